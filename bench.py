@@ -1,14 +1,14 @@
 """Headline benchmark: training rays/sec of the hierarchical NeRF renderer hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--precision bf16x3|bf16|fp32]
+    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--precision bf16x3|bf16|fp32] [--dump-outputs DIR] [--full]
     (N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
      or started plainly, in which case it re-launches itself under torch.distributed.run)
 
 Precision: the measured mode is the product's default, bf16x3 (bf16 MFMA with head + tail operands; outputs within 1e-4 of the
 reference -- measured 2.8e-5 at the metric-depth configs 1 / 2 / 4, profiles/r*_parity_scale.json and `parity_live`; inverse-depth
 passes (config 3) send the last samples of every ray through the fp32 kernels to keep that bound: 1.3e-5; gradients 7e-3 relative
-L2 under a random linear loss, 2e-3 under the photometric loss); the plain bf16 throughput mode and the fp32-MFMA mode are
-measured briefly and reported in `other_modes` on the same line.
+L2 under a random linear loss, 2e-3 under the photometric loss); with --full the plain bf16 throughput mode and the fp32-MFMA mode
+are measured briefly and reported in `other_modes` on the same line.
 
 One step = one optimiser-ready training iteration on synthetic data of the chosen BASELINE.json
 config (bench_workloads.py): config 1 (default, the config the metric is quoted on) = 4096 rays x
@@ -17,7 +17,13 @@ passes, photometric MSE loss on rgb and rgb_fine, gradient all-reduce when N > 1
 clipping + Adam on both networks.  Inputs are resident in HBM before the timed region.  Each rank
 renders its own ray batch (weak scaling).
 
-The JSON line also carries
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs if --dump-outputs is given
+(DIR/<name>.npy: the loss, the render result of the step's main render call, every parameter after the update and its
+gradient; float32, or float64 for the loss and integer outputs; at most 64 MB, larger arrays as a fixed seeded sample) and prints
+one JSON line: `value` rays/s over the K steps, `ms_per_step` the milliseconds one of them took.  Inputs are seeded: the same
+arguments give the same inputs in every run.
+
+With --full the JSON line also carries
   roofline     : dominant kernel (by time per step) vs its MI355X bound -- algorithmic flops (or
                  bytes) per launch / average launch duration measured here with stream events
                  around single-kernel launches (C ABI sparf_launch_kernel) / the guide's peak
@@ -34,7 +40,10 @@ The JSON line also carries
   parity_live  : one 4096-ray config-1 render + backward of THIS run against the float64 referee (on the
                  GPU, ~2 s); `parity` = the committed bounds over all four configs (profiles/r*_parity_scale.json);
   sustained    : after the K contract steps the same step loop runs on for >= --min-seconds with one
-                 event per step: rays/s over the whole loop and over its last second, ms/step p50 / p95.
+                 event per step: rays/s over the whole loop and over its last second, ms/step p50 / p95;
+  other_sizes  : 512 / 1024 / 2048 / 4096 rays per step, eager and as one hipGraph;
+  telemetry    : clock / power while the steps ran and the calibration kernels before and after (bench_telemetry.py);
+  scaling_legs : N > 1: the contract line is the weak leg, a short strong leg (--rays / N per GPU) follows.
 """
 import argparse
 import contextlib
@@ -522,6 +531,35 @@ def reduce_leg(dt, nrays, steps, world, device):
                 per_rank_ms_per_step=rank_ms, seconds=dt_all)
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(w, loss, out_dir):
+    """What the last timed step handed its caller, as DIR/<name>.npy: the loss, the step's main render result (render.<key>), every
+    parameter after the update (param.<name>) and its gradient (grad.<name>).  Floating tensors as float32, the loss and integer
+    tensors as float64.  Over DUMP_BYTES in all, every array above an equal share is cut to that many elements, drawn by a fixed seed."""
+    import numpy as np
+    arrays = {"loss": loss.detach().double()}
+    for k, v in sorted((w.last_render or {}).items()):
+        if torch.is_tensor(v):
+            arrays[f"render.{k}"] = v.detach()
+    for n, p in w.graph.named_parameters():
+        arrays[f"param.{n}"] = p.detach()
+        if p.grad is not None:
+            arrays[f"grad.{n}"] = p.grad.detach()
+    arrays = {k: (v.float() if v.is_floating_point() and v.dtype != torch.float64 else v.double()).cpu().numpy().reshape(-1)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        share = DUMP_BYTES // 8 // len(arrays)             # elements per array, at 8 bytes each in the worst case
+        for k, a in arrays.items():
+            if a.size > share:
+                arrays[k] = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -559,6 +597,12 @@ def main():
     ap.add_argument("--no-other-modes", action="store_true", help="skip the brief measurements of the other precision modes")
     ap.add_argument("--no-other-sizes", action="store_true", help="skip the small-batch measurements (512 / 1024 / 2048 rays per step, eager and as one hipGraph)")
     ap.add_argument("--graph", action="store_true", help="configs 1 / 2, one GPU: replay the whole step as ONE captured hipGraph (Workload.capture) in the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0; at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: telemetry + calibration kernels, the sustained loop, the strong leg (N > 1), "
+                         "roofline + live PMC, live parity, other modes and sizes, psnr_vs_ref, CPU baseline, the committed parity profiles; "
+                         "the --no-* / --min-seconds options select among them")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -608,6 +652,7 @@ def main():
         return w
 
     w = make(args.precision)
+    w.keep_outputs = bool(args.dump_outputs) and rank == 0
     torch.cuda.manual_seed(1234 + rank)                                # each rank: its own ray shard / draws
     if use_graph:
         w.step = w.capture()                                           # the same iteration, replayed as one hipGraph
@@ -641,7 +686,7 @@ def main():
     # library's two fixed calibration kernels before and after the measurement (rank 0; every rank idles behind the barrier meanwhile)
     sampler = calib = None
     box = {}
-    if rank == 0 and not args.no_telemetry:
+    if args.full and rank == 0 and not args.no_telemetry:
         import bench_telemetry as BT
         sampler = BT.Sampler(local).start()
         try:
@@ -658,10 +703,12 @@ def main():
     contract_step_ms = timed.step_ms
     leg = reduce_leg(dt, nrays, args.steps, world, device)
     rank_ms, dt, nrays_all, value = leg["per_rank_ms_per_step"], leg["seconds"], leg["rays_per_step_all_ranks"] * args.steps, leg["value"]
+    if w.keep_outputs:
+        dump_outputs(w, loss, args.dump_outputs)
     # sustained loop: the same steps for >= --min-seconds, one event per step (the contract region above is 0.15 s at
     # K = 20: a burst on a chip that clocks down under MFMA load)
     sustained = None
-    if args.min_seconds > 0:
+    if args.full and args.min_seconds > 0:
         n_sus = max(args.steps, int(math.ceil(args.min_seconds / (dt / args.steps))))      # from the rank-reduced dt: the same count on every rank
         evs, rays_seq = [torch.cuda.Event(enable_timing=True)], []
         with win("sustained"):
@@ -697,7 +744,7 @@ def main():
     # N > 1: ONE driver command yields both scaling numbers SURVEY 8e asks for -- the contract line above is the weak leg
     # (--rays per GPU), then a short strong leg: the same global batch split over the ranks (--rays / N per GPU)
     scaling_legs = None
-    if world > 1 and not args.strong and not args.no_strong_leg:
+    if args.full and world > 1 and not args.strong and not args.no_strong_leg:
         weak = dict(leg, rays_per_gpu_per_step=nrays / max(1, args.steps))
         r_strong = max(SHAPES[args.config]["B"], args.rays // world)
         ws = Workload(args.config, args.precision, device, rays=r_strong, optimizer=args.optimizer, batched=args.batched, bucket_factory=buckets_for,
@@ -755,7 +802,7 @@ def main():
         # whole-step algorithmic MFMA fraction: rays/s x 810.8 MFLOP / dense peak of the operand type
         "mfma_fraction_of_step": value / world * FLOP_TRAIN_RAY / (PEAK[args.precision] * 1e12) if args.config in (1, 2) else None,
     }
-    if rank == 0:
+    if args.full and rank == 0:
         replayed = {}          # everything on this line that was NOT measured by this run (committed profiles of other sessions), in one place
         if sampler is not None:
             sampler.stop()
@@ -844,6 +891,7 @@ def main():
         if replayed:
             replayed["note"] = "figures of committed profiles measured in other sessions / on other machines; nothing else on this line is replayed"
             line["replayed_from_profiles"] = replayed
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

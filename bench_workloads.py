@@ -243,6 +243,9 @@ class Workload:
         self.net_params = [p for net in nets for n, p in net.named_parameters() if n != "progress"]
         self.buckets = bucket_factory(self) if bucket_factory is not None else None
         self.rays_last = self.rays_fwd_only_last = 0
+        # keep_outputs: the step keeps its main render result in `last_render` (bench.py --dump-outputs); off, the step holds no
+        # reference to its outputs once it returns
+        self.keep_outputs, self.last_render = False, None
         # static synthetic correspondences for configs 3 / 4: pixel lists of a view pair, matched through a plane at depth 3
         if config in (3, 4):
             g = torch.Generator().manual_seed(seed + 2)
@@ -408,6 +411,8 @@ class Workload:
         pose = g.get_w2c_pose(opt, d, mode="train") if self.config != 1 else d.pose
         ret = g.render(opt, pose, H=self.H, W=self.W, intr=self.intr, ray_idx=ray_idx, depth_range=g._depth_range(opt, d), iter=it, mode="train")
         loss = self._photometric(ret, ray_idx)
+        if self.keep_outputs:
+            self.last_render = ret
         loss.backward()
         if update:
             self.optim.step()
@@ -456,6 +461,8 @@ class Workload:
             loss = self._photometric(ret, ray_idx) + 1e-3 * loss_c + 1e-3 * loss_d      # loss_weight.corres = depth_cons = -3 (10^)
             nrays = self.B * R + sum(q["pixels"].shape[0] for q in reqs) + n_last
             self.rays_fwd_only_last = n_max
+        if self.keep_outputs:
+            self.last_render = ret
         loss.backward()
         if self.buckets is not None:
             self.buckets(loss)

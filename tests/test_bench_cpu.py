@@ -1,5 +1,5 @@
 """Host-side pieces of bench.py that need no GPU: which committed profile a line quotes (newest ROUND, not the
-lexicographically largest name -- r100 > r99, r03b > r03), the stale-kernel flag, the PMC traffic lookup."""
+lexicographically largest name -- r100 > r99, r03b > r03), the stale-kernel flag, the PMC traffic lookup, the output dump."""
 import json
 import os
 
@@ -129,3 +129,33 @@ with open(os.path.join(out_dir, "host", "123", name + "_counter_collection.csv")
     monkeypatch.setenv("ROCP_TOOL_LIBRARIES", "/opt/rocm/lib/rocprofiler-sdk/librocprofiler-sdk-tool.so")        # bench.py itself under rocprofv3: no nested profiler
     total, how = bench.live_pmc_traffic("mlp_fwd", "bf16x3", 786432)
     assert total is None and "nested" in how
+
+
+def test_dump_outputs_types_names_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the loss, the step's render result, every parameter and its gradient as <name>.npy; float32 (float64
+    for the loss and integer outputs); over the byte budget, large arrays are cut to the same fixed seeded sample in every run"""
+    import numpy as np
+    import torch
+
+    class W:
+        pass
+
+    w = W()
+    w.graph = torch.nn.Linear(300, 200)
+    w.graph(torch.ones(1, 300)).sum().backward()
+    w.last_render = dict(rgb=torch.rand(64, 3), ray_idx=torch.arange(64), note="not a tensor")
+    loss = torch.tensor(0.25)
+    bench.dump_outputs(w, loss, str(tmp_path / "a"))
+    got = {p.name[:-4]: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["grad.bias", "grad.weight", "loss", "param.bias", "param.weight", "render.ray_idx", "render.rgb"]
+    assert got["loss"].dtype == np.float64 and float(got["loss"][0]) == 0.25 and got["render.ray_idx"].dtype == np.float64
+    assert got["param.weight"].dtype == np.float32 and np.array_equal(got["param.weight"], w.graph.weight.detach().numpy().reshape(-1))
+    assert np.array_equal(got["grad.bias"], np.ones(200, np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)           # 64 KiB: the 60 000-element weight and its gradient must be sampled
+    for d in ("b", "c"):
+        bench.dump_outputs(w, loss, str(tmp_path / d))
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    c = {p.name: np.load(p) for p in (tmp_path / "c").iterdir()}
+    assert sum(a.nbytes for a in b.values()) <= 64 << 10 and b["param.weight.npy"].size < 60000
+    assert all(np.array_equal(b[k], c[k]) for k in b)
+    assert np.array_equal(b["render.rgb.npy"], got["render.rgb"])          # small arrays stay whole

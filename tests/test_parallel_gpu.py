@@ -170,7 +170,7 @@ def test_bench_self_launches_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SPARF_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", "512", "--config", "2",
-                        "--no-roofline", "--no-cpu-baseline", "--no-other-modes", "--no-psnr"], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--no-roofline", "--no-cpu-baseline", "--no-other-modes", "--no-psnr"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["value"] > 0 and lines[0]["config"]["baseline_config"] == 2

@@ -1,7 +1,7 @@
 #!/bin/bash
 # one quick bench line per call: value, sustained value, the calibration figures and the normalised figures (box-to-box survey; gpurun leases land on different GPUs)
 cd ${GRAFT_REPO_ROOT:-.}
-python bench.py --no-cpu-baseline --no-psnr --no-other-modes --no-other-sizes --no-live-parity --no-live-pmc --steps 30 2>/dev/null | python -c '
+python bench.py --full --no-cpu-baseline --no-psnr --no-other-modes --no-other-sizes --no-live-parity --no-live-pmc --steps 30 2>/dev/null | python -c '
 import json, sys
 d = json.loads(sys.stdin.read()); b = d["config"]["box"]; k = d["roofline"]["all_kernels"]
 print(json.dumps(dict(device=d["telemetry"]["device"], value=round(d["value"]), sustained=round(d["sustained"]["value"]), calib_mfma=round(b["calib_mfma_tflops"], 1),

@@ -3,6 +3,8 @@
 # point instead of forty session scripts).  Run on the GPU box from the repository root, e.g.
 #     gpurun --timeout 900 -- 'bash tools/evidence.sh tests tape'
 # Every section writes gpurun_out/r06_<name>.*; copy what is to be judged into profiles/.
+# The sections `bench` and `configs` write to $EVIDENCE_OUT (default evidence_out/).  Every bench.py call here runs with --full: the
+# sections quote what a plain bench.py run leaves out (sustained loop, roofline, telemetry, ...).
 #
 #   tests        pytest -m gpu (the whole suite, no -x) + smoke()                                   -> r06_pytest_gpu.log
 #   tape         the committed reference tapes replayed on the HIP renderer (also part of `tests`)   -> r06_reference_tape.json
@@ -34,7 +36,9 @@ TAG=${TAG:-r06}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 REFZIP=oracle/_ref/reference_tree.zip
-quick="--no-cpu-baseline --no-psnr --no-other-modes --no-other-sizes --no-live-parity --no-live-pmc"
+quick="--full --no-cpu-baseline --no-psnr --no-other-modes --no-other-sizes --no-live-parity --no-live-pmc"
+OUT=${EVIDENCE_OUT:-evidence_out}
+mkdir -p "$OUT"
 for sec in "$@"; do
   echo "=================== $sec"
   case $sec in
@@ -62,13 +66,13 @@ PY
     host)
       timeout 600 python tests/tools/host_overhead.py bf16x3 --profile 2>&1 | grep -v "Warning\|warnings.warn" | tee gpurun_out/${TAG}_host_overhead.log | head -110 ;;
     bench)
-      timeout 900 python bench.py > gpurun_out/${TAG}_bench_bf16x3.json 2> gpurun_out/${TAG}_bench_bf16x3.err; cut -c1-600 gpurun_out/${TAG}_bench_bf16x3.json; tail -3 gpurun_out/${TAG}_bench_bf16x3.err ;;
+      timeout 900 python bench.py --full > "$OUT/${TAG}_bench_bf16x3.json" 2> "$OUT/${TAG}_bench_bf16x3.err"; cut -c1-600 "$OUT/${TAG}_bench_bf16x3.json"; tail -3 "$OUT/${TAG}_bench_bf16x3.err" ;;
     benchquick)
       timeout 600 python bench.py $quick --steps 30 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print("config 1:", round(d["value"]), "rays/s", round(d["ms_per_step"],3), "ms;", {k:(v["launch_ms"]) for k,v in d["roofline"]["all_kernels"].items()}, "sustained", d["sustained"] and round(d["sustained"]["value"]))' ;;
     configs)
       for c in 2 3 4; do
-        timeout 500 python bench.py --config $c --no-cpu-baseline --no-psnr --no-roofline --no-other-sizes --no-other-modes --no-live-parity --steps 20 > gpurun_out/${TAG}_bench_c$c.json 2> gpurun_out/${TAG}_bench_c$c.err
-        python -c 'import sys,json; d=json.loads(open(sys.argv[1]).read()); print("config", sys.argv[2], round(d["value"]), "rays/s", round(d["ms_per_step"],2), "ms; sustained", d["sustained"] and round(d["sustained"]["value"]))' gpurun_out/${TAG}_bench_c$c.json $c || tail -3 gpurun_out/${TAG}_bench_c$c.err
+        timeout 500 python bench.py --full --config $c --no-cpu-baseline --no-psnr --no-roofline --no-other-sizes --no-other-modes --no-live-parity --steps 20 > "$OUT/${TAG}_bench_c$c.json" 2> "$OUT/${TAG}_bench_c$c.err"
+        python -c 'import sys,json; d=json.loads(open(sys.argv[1]).read()); print("config", sys.argv[2], round(d["value"]), "rays/s", round(d["ms_per_step"],2), "ms; sustained", d["sustained"] and round(d["sustained"]["value"]))' "$OUT/${TAG}_bench_c$c.json" $c || tail -3 "$OUT/${TAG}_bench_c$c.err"
       done ;;
     kernels)
       for P in ${KERNEL_PRECS:-bf16x3 bf16x3+q8 bf16 bf16+q8}; do timeout 300 python tools/kernel_bench.py $P 2>&1 | grep -v "Warning\|warnings.warn\|amdgpu.ids"; done | tee gpurun_out/${TAG}_kernel_bench.log ;;
