@@ -304,6 +304,14 @@ int sparf_calib_hbm(const void* src, void* dst, int64_t bytes, int mode, float* 
  * rows_total sample rows whose active range (segments with an upstream gradient) covers rows_active rows.  nsplit_total is
  * what sparf_bwd_workspace_bytes reserved partial blocks for; nsplit_active <= nsplit_total always holds. */
 int sparf_debug_wgrad_split(int64_t rows_total, int64_t rows_active, int* nsplit_total, int* nsplit_active, int* rows_per_split_active);
+/* Host arithmetic only (tests): byte offsets inside the workspace of sparf_pass_backward, in the order they are carved:
+ * out = {gradient area, d_sigma, d_z, d_len, split-K partial blocks, dp, dv, total}; total = sparf_bwd_workspace_bytes; dp == dv ==
+ * total for a pass without pose gradients.  `prec` may carry SPARF_SAVE_Q8. */
+int sparf_debug_bwd_workspace(int prec, int nrays, int nsamp, int pose, int64_t out[8]);
+/* Host arithmetic only (tests): the launch plan of the bf16x3 data-gradient kernel over `rows` active rows: the leading *rows8 rows
+ * (0, rows, or a whole number of rounds of 256-row tiles over *cus compute units) run in the 8-wave kernel, the rest in the 4-wave
+ * kernel.  *cus is the compute-unit count of the current device, 256 where there is none. */
+int sparf_debug_x3_dgrad_plan(int64_t rows, int64_t* rows8, int* cus);
 
 #ifdef __cplusplus
 }

@@ -504,6 +504,24 @@ int sparf_debug_wgrad_split(int64_t rows_total, int64_t rows_active, int* nsplit
     return 0;
 }
 
+// Host arithmetic only (tests): the byte offsets of a backward workspace (bwd_ws_layout above) in the order they are carved,
+// out = {gradient area, d_sigma, d_z, d_len, partial blocks, dp, dv, total = sparf_bwd_workspace_bytes}
+int sparf_debug_bwd_workspace(int prec, int nrays, int nsamp, int pose, int64_t out[8]) {
+    const PassPrec pp = pass_prec(prec);
+    if (!pp.ok || nrays < 0 || nsamp <= 0 || !out) return 1;
+    const BwdWs w = bwd_ws_layout(pp.af, nrays, nsamp, pose);
+    out[0] = w.grad; out[1] = w.d_sigma; out[2] = w.d_z; out[3] = w.d_len; out[4] = w.partial; out[5] = w.dp; out[6] = w.dv; out[7] = w.total;
+    return 0;
+}
+// Host arithmetic only (tests): the launch plan of the bf16x3 data-gradient kernel over `rows` active rows (x3_dgrad_rows8 above):
+// rows [0, rows8) in 8 waves, [rows8, rows) in 4; `cus` = the CU count the plan was made for (256 where there is no device)
+int sparf_debug_x3_dgrad_plan(int64_t rows, int64_t* rows8, int* cus) {
+    if (rows < 0 || !rows8 || !cus) return 1;
+    *rows8 = x3_dgrad_rows8(rows);
+    *cus = num_cus();
+    return 0;
+}
+
 int sparf_launch_kernel(int which, const sparf_pass_fwd_t* f, const sparf_pass_bwd_t* b, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (which == 0) {

@@ -16,14 +16,11 @@ import torch
 from oracle import nerf_oracle as O
 from sparf_amd import lib as L
 from sparf_amd import ops
+from tests.backward_referee import decode_save as _decode          # save area -> (X [rows, 2272] canonical float32, mask words [tiles, 9, 64, 4])
 from tests.golden.recipe import small_opt, make_state_dict
 from tests.test_hip_gpu import dev, make_scene, params_list, rel_err, rel_l2
 
 pytestmark = pytest.mark.gpu
-
-# csrc/layout.h: saved buffers (columns) of a row, in order; 32-row tile blocks [buffer][16-byte chunk][row][CH elements] + 9 mask KiB
-SAVE_BUFS = [320, 256, 256, 256, 256, 256, 256, 288, 128]
-SAVE_COLS = sum(SAVE_BUFS)
 
 
 def _inputs(R, N, seed):
@@ -67,29 +64,6 @@ def _forward_save(prec, far, sd, center, dirs, t):
     L.check(lib.sparf_pass_forward(ctypes.byref(a), L.stream_ptr(d)), "fwd")
     torch.cuda.synchronize()
     return out, save
-
-
-def _decode(save, rows, fp32):
-    """save area -> (X [rows, 2272] as float32 in canonical (buffer, half h, slot q) order, masks [tiles, 9, 64, 4] int32)"""
-    eb, ch = (4, 4) if fp32 else (2, 8)
-    tile_bytes = SAVE_COLS * 32 * eb + 9 * 1024
-    ntiles = save.numel() // tile_bytes
-    blocks = save[:ntiles * tile_bytes].view(ntiles, tile_bytes)
-    cols, off = [], 0
-    for C in SAVE_BUFS:
-        raw = blocks[:, off * 32 * eb:(off + C) * 32 * eb].contiguous()
-        vals = raw.view(torch.float32 if fp32 else torch.bfloat16).view(ntiles, C // ch, 32, ch).float()      # [tile][chunk][row][el]
-        x = vals.permute(0, 2, 1, 3).reshape(ntiles * 32, C)                                                 # [row][pos]
-        # pos -> (h, q): pos = (q // ch) * 2ch + h * ch + q % ch
-        pos = torch.arange(C, device=save.device)
-        q = (pos // (2 * ch)) * ch + pos % ch
-        h = (pos // ch) % 2
-        order = torch.argsort(h * (C // 2) + q)                 # canonical column = h * (C/2) + q
-        cols.append(x[:, order])
-        off += C
-    X = torch.cat(cols, dim=1)[:rows]
-    masks = blocks[:, SAVE_COLS * 32 * eb:].contiguous().view(torch.int32).view(ntiles, 9, 64, 4)
-    return X, masks
 
 
 @pytest.mark.parametrize("K", [1, 8])

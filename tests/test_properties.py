@@ -231,7 +231,18 @@ def test_gpu_ray_segments_at_the_row_counts_where_the_data_gradient_kernel_chang
     """The same property at the sizes where the bf16x3 data-gradient launch is planned per row count (api.hip x3_dgrad_rows8, round 6):
     64 samples per ray with the first `first` rays inactive leave an active range that starts inside the pass (`row_begin` > 0, on a
     256-row tile boundary or not) and is, in turn, 1.5 rounds of 256-row tiles (the full round in 8 waves + the remainder in 4: two
-    launches that must meet exactly at row_begin + 65 536), one-and-a-bit rounds, and less than one round (all in 4 waves)."""
+    launches that must meet exactly at row_begin + 65 536), one-and-a-bit rounds, and less than one round (all in 4 waves).
+    Which plan each case gets is asked of the library (sparf_debug_x3_dgrad_plan: host arithmetic on the CU count of this device)
+    and asserted, so that the test cannot silently stop exercising the hybrid launch."""
+    import ctypes
+    from sparf_amd import lib as L
+    rows8, cus = ctypes.c_int64(), ctypes.c_int()
+    active = (R - first) * 64
+    assert L.load().sparf_debug_x3_dgrad_plan(active, ctypes.byref(rows8), ctypes.byref(cus)) == 0
+    plan = "all8" if rows8.value == active else "all4" if rows8.value == 0 else "hybrid"
+    want = {(1600, 70): "hybrid", (1600, 64): "hybrid", (1100, 1): "hybrid", (600, 88): "all4"}[(R, first)]
+    assert plan == want and rows8.value % (256 * cus.value) == 0, \
+        f"{active} active rows on {cus.value} CUs: {rows8.value} rows planned in 8 waves ({plan}), the case is written for {want}"
     _segments_case(R, 64, 11, [first], 0b10, pose, 0, False, x3=True)
 
 

@@ -16,85 +16,11 @@ import torch
 from oracle import nerf_oracle as O
 from sparf_amd import lib as L
 from sparf_amd import ops
+from tests.backward_referee import SAVE_BUFS, GRAD_BUFS, decode_planes, decode_q8, encode_planes, dequantise      # (the area decoders live there, once)
 from tests.golden.recipe import small_opt, make_state_dict
 from tests.test_hip_gpu import dev, make_scene, params_list
 
 pytestmark = pytest.mark.gpu
-
-SAVE_BUFS = [320, 256, 256, 256, 256, 256, 256, 288, 128]                 # csrc/layout.h SaveBuf
-GRAD_BUFS = [256] * 7 + [288, 128, 32]                                   # csrc/layout.h GradBuf
-
-
-def _canon(x, C, ch):
-    """[rows][pos] -> canonical column = h * (C / 2) + q, pos = (q // ch) * 2 ch + h * ch + q % ch (layout.h pos_of)"""
-    pos = torch.arange(C, device=x.device)
-    q = (pos // (2 * ch)) * ch + pos % ch
-    h = (pos // ch) % 2
-    return x[:, torch.argsort(h * (C // 2) + q)]
-
-
-def decode_planes(area, bufs, n_mask_kib):
-    """bf16 plane area -> ([rows_padded, sum(bufs)] float32 in canonical order per buffer, mask bytes per tile)"""
-    cols = sum(bufs)
-    tile_bytes = cols * 32 * 2 + n_mask_kib * 1024
-    ntiles = area.numel() // tile_bytes
-    blocks = area[:ntiles * tile_bytes].view(ntiles, tile_bytes)
-    out, off = [], 0
-    for C in bufs:
-        raw = blocks[:, off * 64:(off + C) * 64].contiguous()
-        vals = raw.view(torch.bfloat16).view(ntiles, C // 8, 32, 8).float()                  # [tile][chunk][row][el]
-        out.append(_canon(vals.permute(0, 2, 1, 3).reshape(ntiles * 32, C), C, 8))
-        off += C
-    return torch.cat(out, dim=1), blocks[:, cols * 64:cols * 64 + n_mask_kib * 1024]
-
-
-def decode_q8(area, bufs, n_mask_kib):
-    """8-bit area -> (u [rows_padded, sum(bufs)] int32 canonical, steps [rows_padded, len(bufs), 2] float32, mask bytes per tile)"""
-    cols = sum(bufs)
-    tile_bytes = cols * 32 + n_mask_kib * 1024 + len(bufs) * 256
-    ntiles = area.numel() // tile_bytes
-    blocks = area[:ntiles * tile_bytes].view(ntiles, tile_bytes)
-    out, off = [], 0
-    for C in bufs:
-        raw = blocks[:, off * 32:(off + C) * 32].contiguous().view(ntiles, C // 32, 2, 32, 16)     # [tile][block][h][row][slot in block]
-        u = raw.permute(0, 3, 2, 1, 4).reshape(ntiles * 32, C).int()                               # [row][h][block][slot] = h * C/2 + q
-        out.append(u)
-        off += C
-    so = cols * 32 + n_mask_kib * 1024
-    steps = blocks[:, so:so + len(bufs) * 256].contiguous().view(torch.float32).view(ntiles, len(bufs), 2, 32)
-    steps = steps.permute(0, 3, 1, 2).reshape(ntiles * 32, len(bufs), 2)
-    return torch.cat(out, dim=1), steps, blocks[:, cols * 32:so]
-
-
-def encode_planes(X, bufs, tail):
-    """inverse of decode_planes: canonical-order values [rows_padded, sum(bufs)] -> bf16 plane area bytes; `tail`: the bytes that follow
-    the planes in every tile block (mask words), [ntiles, n] uint8"""
-    ntiles = X.shape[0] // 32
-    parts, off = [], 0
-    for C in bufs:
-        pos = torch.arange(C, device=X.device)
-        q = (pos // 16) * 8 + pos % 8
-        h = (pos // 8) % 2
-        order = torch.argsort(h * (C // 2) + q)
-        x = torch.empty(X.shape[0], C, device=X.device)
-        x[:, order] = X[:, off:off + C]
-        vals = x.view(ntiles, 32, C // 8, 8).permute(0, 2, 1, 3).contiguous().to(torch.bfloat16)
-        parts.append(vals.view(torch.uint8).reshape(ntiles, C * 64))
-        off += C
-    return torch.cat(parts + [tail], dim=1).reshape(-1)
-
-
-def dequantise(U, S, bufs):
-    """what the weight-gradient kernel multiplies out: bf16(fma(u, step, -128 step)), canonical order, as float32"""
-    out, off = [], 0
-    for b, C in enumerate(bufs):
-        half = C // 2
-        part = ((torch.arange(C, device=U.device) % half) >= 128).long()
-        st = S[:, b, :][:, part].double()                                                # [rows, C]
-        v = (U[:, off:off + C].double() * st - 128.0 * st).float()                       # exact in float64, one rounding to float32 = the FMA
-        out.append(v.to(torch.bfloat16).float())
-        off += C
-    return torch.cat(out, dim=1)
 
 
 def quantise(X, bufs):

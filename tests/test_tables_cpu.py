@@ -160,3 +160,41 @@ def test_wgrad_split_of_an_active_range_fits_the_workspace():
         assert 1 <= a <= t <= 128, (total, active, t, a)
         assert r % 64 == 0 and r >= 64 and a * r >= active, (total, active, a, r)
         assert (a - 1) * r < max(active, 1), (total, active, a, r)      # no empty trailing split
+
+
+def test_debug_exports_of_the_backward_plan_and_workspace():
+    """Host arithmetic behind tests/test_backward_links_gpu.py.  sparf_debug_x3_dgrad_plan: the leading rows8 rows of the active range
+    go through the 8-wave data-gradient kernel, the rest through the 4-wave kernel: the plan covers [0, rows), and rows8 is 0, rows,
+    or a whole number of rounds of 256-row tiles over the CU count it reports (256 where there is no device).
+    sparf_debug_bwd_workspace: the offsets increase in carving order and end at sparf_bwd_workspace_bytes."""
+    import ctypes
+    import numpy as np
+    lib = L.load()
+    r8, cus = ctypes.c_int64(), ctypes.c_int()
+    seen = set()
+    rs = np.random.RandomState(1)
+    for rows in [0, 1, 2, 15, 1680, 21312, 32768, 32960, 65536, 65537, 98304, 131072, 786432, 1 << 27] + [int(v) for v in rs.randint(1, 1 << 21, size=400)]:
+        assert lib.sparf_debug_x3_dgrad_plan(rows, ctypes.byref(r8), ctypes.byref(cus)) == 0
+        assert cus.value > 0 and 0 <= r8.value <= rows, (rows, r8.value)
+        assert r8.value in (0, rows) or (r8.value % (256 * cus.value) == 0 and rows - r8.value < 256 * cus.value), (rows, r8.value, cus.value)
+        seen.add("all8" if r8.value == rows else "all4" if r8.value == 0 else "hybrid")
+    assert seen == {"all8", "all4", "hybrid"}
+    c = cus.value                         # the cases tests/test_backward_links_gpu.py derives from the CU count
+    for rows, want in ((128 * c, 0), (384 * c, 256 * c), (128 * c + 64, 128 * c + 64)):
+        assert lib.sparf_debug_x3_dgrad_plan(rows, ctypes.byref(r8), ctypes.byref(cus)) == 0 and r8.value == want, (rows, r8.value)
+    assert lib.sparf_debug_x3_dgrad_plan(-1, ctypes.byref(r8), ctypes.byref(cus)) == 1
+    out = (ctypes.c_int64 * 8)()
+    for prec in (L.PREC_BF16, L.PREC_FP32, L.PREC_X3, L.PREC_BF16 | L.SAVE_Q8, L.PREC_X3 | L.SAVE_Q8):
+        for nrays, nsamp in ((1, 2), (3, 5), (70, 24), (333, 64), (1536, 64), (4096, 192)):
+            for pose in (0, 1):
+                assert lib.sparf_debug_bwd_workspace(prec, nrays, nsamp, pose, out) == 0
+                o = list(out)
+                rows = nrays * nsamp
+                assert o[0] == 0 and all(v % 256 == 0 for v in o) and o[7] == lib.sparf_bwd_workspace_bytes(prec, nrays, nsamp, pose)
+                assert o[0] < o[1] < o[2] < o[3] < o[4] < o[5] <= o[6] <= o[7], o
+                assert o[2] - o[1] >= 4 * rows and o[3] - o[2] >= 12 * rows and o[4] - o[3] >= 4 * nrays
+                if pose:
+                    assert o[6] - o[5] >= 12 * rows and o[7] - o[6] >= 128 * rows
+                else:
+                    assert o[5] == o[6] == o[7]
+    assert lib.sparf_debug_bwd_workspace(L.PREC_FP32 | L.SAVE_Q8, 16, 64, 0, out) == 1
