@@ -173,29 +173,40 @@ enum { PIPE_LDS_BYTES = 2 * CHUNK_MAX_BYTES };
 template <int NWAVES, bool SPREAD = false> struct WeightPipe {
     __amdgpu_buffer_rsrc_t rsrc;   // packed stream (global), addressed as raw buffer
     char* lds;                     // 2 * CHUNK_MAX_BYTES
+    char* lds_w;                   // lds + wave * 1024: where this wave's piece 0 of buffer 0 lands
     int wave, lane16;
     unsigned parity;
     Prof prof;
 
+    // The wave's share of a piece's address -- wave * 1024, in the stream and in LDS -- is folded ONCE into the wave's own descriptor
+    // base and LDS base, so that what is left per piece is the integer constant OFF + I * NWAVES * 1024: a literal the compiler
+    // rematerialises (s_mov_b32) where it is used.  With `wave` inside the scalar offset every one of the ~530 pieces of a tile
+    // owned a distinct loop-invariant scalar; hipcc computed them all in front of the tile loop, parked them in VGPR lanes (502
+    // spilled SGPRs in the bf16x3 training forward) and paid a v_readlane_b32 plus the wait states between a VALU-written SGPR and
+    // the vector-memory instruction that reads it in front of every piece.  (In the descriptor and not in the per-lane offset:
+    // lane * 16 is also the lane part of the mask-word accesses, one VGPR for both.)
+    // Range check (raw buffer, stride 0): the unit compares the per-lane offset, not the scalar one, with the descriptor's size, so
+    // it never was what keeps a piece inside its chunk -- the `o < BYTES` guards are, and they are unchanged; the size shrinks by
+    // what the base advanced, lane16 < 1 KiB is inside every stream.
     SP_DEV void init(const char* g, unsigned stream_bytes, char* l) {
         prof.start();
-        rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g, 0, stream_bytes, 0x00020000);
+        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(g + wave * 1024), 0, stream_bytes - wave * 1024, 0x00020000);
         lane16 = (threadIdx.x & 63) * 16;
         lds = l;
-        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        lds_w = l + wave * 1024;
         parity = 0;
     }
     // issue this wave's share of chunk [off, off+bytes) into buffer `buf`:
     // buffer_load_dwordx4 ... offen lds  (LDS-DMA, 1 KiB per wave-instruction, address
     // = descriptor base + scalar offset + lane*16, destination = M0 + lane*16)
     SP_DEV void fetch(int off, int bytes, unsigned buf) {
-        char* dst = lds + buf * CHUNK_MAX_BYTES;
+        char* dst = lds_w + buf * CHUNK_MAX_BYTES;
 #pragma unroll
         for (int i = 0; i < CHUNK_MAX_BYTES / (NWAVES * 1024); ++i) {
-            int o = (i * NWAVES + wave) * 1024;
-            if (o < bytes)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(dst + o), 16,
-                                                         lane16, off + o, 0, 0);
+            if ((i * NWAVES + wave) * 1024 < bytes)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(dst + i * NWAVES * 1024), 16,
+                                                         lane16, off + i * NWAVES * 1024, 0, 0);
         }
     }
     // one 1 KiB piece (index I of this wave) of chunk [OFF, OFF+BYTES) into buffer `buf`.  OFF / BYTES / I are
@@ -203,10 +214,10 @@ template <int NWAVES, bool SPREAD = false> struct WeightPipe {
     // instructions per 128-row tile of the bf16x3 forward, each an issue slot of the SIMD's only wave)
     template <int OFF, int BYTES, int I> SP_DEV void fetch_piece(unsigned buf) {
         if constexpr (I * NWAVES * 1024 < BYTES) {
-            const int o = (I * NWAVES + wave) * 1024;
-            if ((I + 1) * NWAVES * 1024 <= BYTES || o < BYTES) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(lds + buf * CHUNK_MAX_BYTES + o), 16,
-                                                         lane16, OFF + o, 0, 0);
+            constexpr int O = I * NWAVES * 1024;          // the piece of wave 0; this wave's starts wave * 1024 further on
+            if ((I + 1) * NWAVES * 1024 <= BYTES || wave * 1024 < BYTES - O) {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(lds_w + buf * CHUNK_MAX_BYTES + O), 16,
+                                                         lane16, OFF + O, 0, 0);
             }
         }
     }

@@ -299,20 +299,32 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
                 if constexpr (st == 0 || st == 1) {
                     constexpr int r = 2 * pr + st;
                     float x = acc[r];                                // (bit_cast of a vector-element expression reads element 0)
-#if SP_LAZY_ACC_READ
+                    int yi;
                     // Deferred units fetch their element from the accumulator registers themselves: left to the compiler, all 32
                     // v_accvgpr_read of a finished group are hoisted into the gap at the group boundary (29 instructions next to
                     // the barrier and the first fragment reads: ~240 cycles of idle matrix pipe, 36 times per tile).  Only for
                     // deferred units: the hazard recogniser does not see into asm, and a deferred element was written >= one
                     // whole MFMA (32 cycles; 11 wait states needed) earlier, the exposed epilogue of a layer's last group was not.
-                    if constexpr (sizeof...(deferred) > 0 && NW == 4) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(x));     // (volatile: stays in its unit; the 4-wave kernels' accumulators live in AGPRs)
-#endif
-                    int yi = __builtin_bit_cast(int, x);
-                    yi = yi > 0 ? yi : 0;
+                    // ReLU and mask push ride in the same statement: hipcc pads every read of a register an asm statement wrote by the
+                    // instruction or statement right behind it (s_nop 0, 467 per tile; it does so behind an EMPTY statement too: the
+                    // caution is about what the statement might hold -- a transcendental's result needs the wait state -- not about
+                    // v_accvgpr_read_b32, whose result a dependent VALU instruction may read next like any other VALU result).
+                    constexpr bool LAZY = SP_LAZY_ACC_READ && sizeof...(deferred) > 0 && NW == 4;
+                    if constexpr (LAZY && SAVE) {
+                        asm volatile("v_accvgpr_read_b32 %0, %2\n\tv_max_i32 %0, 0, %0\n\tv_cmp_lt_i32 vcc, 0, %0\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc"
+                                     : "=v"(yi), "+v"(mask_bits) : "a"(x) : "vcc");     // (volatile: stays in its unit; the 4-wave kernels' accumulators live in AGPRs)
+                    } else if constexpr (LAZY) {
+                        asm volatile("v_accvgpr_read_b32 %0, %1\n\tv_max_i32 %0, 0, %0" : "=v"(yi) : "a"(x));
+                    } else {
+                        yi = __builtin_bit_cast(int, x);
+                        yi = yi > 0 ? yi : 0;
+                        if constexpr (SAVE)
+                            asm("v_cmp_lt_i32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask_bits) : "v"(yi) : "vcc");
+                    }
                     (st == 0 ? e_v0 : e_v1) = __builtin_bit_cast(float, yi);
-                    if constexpr (SAVE)
-                        asm("v_cmp_lt_i32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask_bits) : "v"(yi) : "vcc");
                 } else if constexpr (st == 2) {
+                    // (the pack stays behind its slot's MFMA: moved up in front of it, next to stage 1's statement, it is padded too)
+                    if constexpr (SP_LAZY_ACC_READ && sizeof...(deferred) > 0 && NW == 4) __builtin_amdgcn_sched_barrier(0);
                     if constexpr (PREC == PREC_FP32) {
                         out[q0] = e_v0;
                         out[q0 + 1] = e_v1;
