@@ -8,6 +8,11 @@ PYTHONPATH to satisfy that import when the real package is absent.
 """
 
 
+def opt_get(node, key, default=None):
+    """node.key of an EasyDict or of a plain namespace; `default` where it has none"""
+    return node.get(key, default) if hasattr(node, "get") else getattr(node, key, default)
+
+
 class EasyDict(dict):
     def __init__(self, d=None, **kwargs):
         super().__init__()

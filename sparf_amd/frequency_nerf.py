@@ -21,6 +21,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from .edict import opt_get
 
 COMPOSITE_KEYS = ("rgb", "rgb_var", "depth", "depth_var", "opacity", "weights", "all_cumulated")
 MAX_ROWS_PER_CALL = 1 << 23          # upper limit of sample rows per pass launch when activations are saved (a memory bound, not an addressing one)
@@ -84,10 +85,8 @@ DEFAULT_FAR_SAMPLES = 8
 
 
 def _hip_get(opt):
-    hip = opt.get("hip", None) if hasattr(opt, "get") else getattr(opt, "hip", None)
-    if hip is None:
-        return lambda k, d=None: d
-    return lambda k, d=None: (hip.get(k, d) if hasattr(hip, "get") else getattr(hip, k, d))
+    hip = opt_get(opt, "hip")
+    return lambda k, d=None: d if hip is None else opt_get(hip, k, d)
 
 
 def precision_name(opt):
@@ -172,6 +171,18 @@ class FrequencyEmbedder:
         spectrum = input[..., None] * freq
         enc = torch.stack([spectrum.sin(), spectrum.cos()], dim=-2)
         return enc.view(*input.shape[:-1], -1)
+
+
+def shape_pass(o, B, R, N):
+    """the flat results of a pass over B x R rays of N samples (ops.PASS_KEYS; or ops.composite's, which has no per-sample ones) in the
+    reference's shapes and key order (frequency_nerf.py:218-226, 317-343).  The depth samples `t` are the caller's to add."""
+    out = {}
+    if "rgb_samples" in o:
+        out.update(rgb_samples=o["rgb_samples"].view(B, R, N, 3), density_samples=o["density_samples"].view(B, R, N))
+    out.update(rgb=o["rgb"].view(B, R, 3), rgb_var=o["rgb_var"].view(B, R, 1), depth=o["depth"].view(B, R, 1),
+               depth_var=o["depth_var"].view(B, R, 1), opacity=o["opacity"].view(B, R, 1), weights=o["weights"].view(B, R, N, 1),
+               all_cumulated=o["all_cumulated"].view(B, R))
+    return out
 
 
 class NeRF(torch.nn.Module):
@@ -341,10 +352,7 @@ class NeRF(torch.nn.Module):
             parts = [ops.nerf_pass(c[i:i + max_rays], d[i:i + max_rays], t[i:i + max_rays],
                                    nz[i:i + max_rays] if nz is not None else None, *args, far=far) for i in range(0, B * R, max_rays)]
             out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
-        return dict(rgb_samples=out["rgb_samples"].view(B, R, N, 3), density_samples=out["density_samples"].view(B, R, N),
-                    rgb=out["rgb"].view(B, R, 3), rgb_var=out["rgb_var"].view(B, R, 1), depth=out["depth"].view(B, R, 1),
-                    depth_var=out["depth_var"].view(B, R, 1), opacity=out["opacity"].view(B, R, 1),
-                    weights=out["weights"].view(B, R, N, 1), all_cumulated=out["all_cumulated"].view(B, R))
+        return shape_pass(out, B, R, N)
 
     # ------------------------------------------------------------------ reference API
     def forward_samples(self, opt, center, ray, depth_samples, embedder_pts, embedder_view, mode=None):
@@ -369,9 +377,7 @@ class NeRF(torch.nn.Module):
         B, R, N = dens.shape
         out = ops.composite(ray.reshape(B * R, 3), dens.reshape(B * R, N), rgb_s.reshape(B * R, N, 3), depth_samples.reshape(B * R, N),
                             bool(opt.nerf.setbg_opaque or opt.mask_img))
-        pred_dict.update(rgb=out["rgb"].view(B, R, 3), rgb_var=out["rgb_var"].view(B, R, 1), depth=out["depth"].view(B, R, 1),
-                         depth_var=out["depth_var"].view(B, R, 1), opacity=out["opacity"].view(B, R, 1), weights=out["weights"].view(B, R, N, 1),
-                         all_cumulated=out["all_cumulated"].view(B, R))
+        pred_dict.update(shape_pass(out, B, R, N))
         return pred_dict
 
     def forward(self, opt, points_3D_samples, ray, embedder_pts, embedder_view, mode=None):

@@ -12,6 +12,11 @@ from . import lib as L
 
 
 _C2F_OFF = {}
+# what a pass returns, in order, under the reference's composite keys; the C structs call the per-sample density plain `density`
+PASS_KEYS = ("rgb", "depth", "opacity", "weights", "depth_var", "rgb_var", "all_cumulated", "density_samples", "rgb_samples")
+RENDER_KEYS = PASS_KEYS + ("t",)
+_PASS_FIELDS = tuple("density" if k == "density_samples" else k for k in PASS_KEYS)
+_GRAD_FIELDS = tuple("g_" + k for k in _PASS_FIELDS)
 
 
 def _f32(t):
@@ -46,11 +51,8 @@ def c2f_weights(progress, barf_c2f, device):
     progress.data every iteration (nerf_trainer.py:273-275), which no version counter sees."""
     lib = L.load()
     L.require_gpu(device)
-    has = barf_c2f is not None
-    if not has:                       # no masking: the constant vector, made once per device
-        dev = torch.device(device)
-        if dev.index is None:         # a bare "cuda" must not bind the cache entry to whichever device was current first
-            dev = torch.device("cuda", torch.cuda.current_device())
+    if barf_c2f is None:              # no masking: the constant vector, made once per device
+        dev = _resolve(device)        # a bare "cuda" must not bind the cache entry to whichever device was current first
         if dev not in _C2F_OFF:       # built on the device (no pageable host->device copy: legal under stream capture)
             v = torch.ones(16, dtype=torch.float32, device=dev)
             v[14:] = 0.0
@@ -58,9 +60,8 @@ def c2f_weights(progress, barf_c2f, device):
         return _C2F_OFF[dev]
     out = torch.empty(16, dtype=torch.float32, device=device)
     prog = _f32(progress).reshape(1).to(device)
-    s, e = (float(barf_c2f[0]), float(barf_c2f[1])) if has else (0.0, 1.0)
     with L.on(device):
-        L.check(lib.sparf_c2f_weights(L.ptr(prog), int(has), s, e, L.ptr(out), L.stream_ptr(device)), "sparf_c2f_weights")
+        L.check(lib.sparf_c2f_weights(L.ptr(prog), 1, float(barf_c2f[0]), float(barf_c2f[1]), L.ptr(out), L.stream_ptr(device)), "sparf_c2f_weights")
     return out
 
 
@@ -93,6 +94,16 @@ def sample_coarse(nrays, nsamp, dmin, scale, inverse, device, jitter=None, u_con
     return t
 
 
+def _fine_grid(lib, u_mid, dev):
+    """(entry point, grid) of a resampling call.  A HOST grid (the reference draws it on the CPU, renderer.py:439) travels in the launch
+    arguments: no host -> device copy; one too long for them is copied to the device after all."""
+    if u_mid.device.type == "cuda":
+        return lib.sparf_sample_fine, u_mid
+    if u_mid.numel() > 256:
+        return lib.sparf_sample_fine, u_mid.to(dev)
+    return lib.sparf_sample_fine_hostgrid, u_mid
+
+
 def sample_fine(weights, t_coarse, u_mid, dmin, dmax, want_unsorted=False, range_dev=None, out=None):
     """weights, t_coarse [R, Nc]; u_mid [Nf].  Returns (sorted union [R, Nc+Nf], t_fine or None).
     out: optional [R, Nc+Nf] destination for the sorted union."""
@@ -104,10 +115,7 @@ def sample_fine(weights, t_coarse, u_mid, dmin, dmax, want_unsorted=False, range
     w, tc, um = _f32(weights), _f32(t_coarse), _f32(u_mid)
     out = torch.empty(R, Nc + Nf, dtype=torch.float32, device=dev) if out is None else _check_out(out, (R, Nc + Nf), dev)
     tf = torch.empty(R, Nf, dtype=torch.float32, device=dev) if want_unsorted else None
-    # a HOST grid (the reference draws it on the CPU, renderer.py:439) travels in the launch arguments: no host -> device copy
-    fn = lib.sparf_sample_fine if um.device.type == "cuda" else lib.sparf_sample_fine_hostgrid
-    if um.device.type != "cuda" and Nf > 256:
-        um, fn = um.to(dev), lib.sparf_sample_fine
+    fn, um = _fine_grid(lib, um, dev)
     with L.on(dev):
         L.check(fn(L.ptr(w), L.ptr(tc), L.ptr(um), L.ptr(range_dev), float(dmin), float(dmax), R, Nc, Nf, L.ptr(tf),
                    L.ptr(out), L.stream_ptr(dev)), "sparf_sample_fine")
@@ -121,20 +129,69 @@ def _segments(segs, grads=None):
     arr = (L.Segment * len(segs))()
     for i, (r0, n, ns) in enumerate(segs):
         arr[i].ray0, arr[i].nrays, arr[i].noise_scale = int(r0), int(n), float(ns)
-        if grads is not None:
-            g = [x.data_ptr() if x is not None else None for x in grads[i]]
-            (arr[i].g_rgb, arr[i].g_depth, arr[i].g_opacity, arr[i].g_weights, arr[i].g_depth_var, arr[i].g_rgb_var, arr[i].g_all_cumulated,
-             arr[i].g_density, arr[i].g_rgb_samples) = g + [None] * (9 - len(g))
+        for k, x in zip(_GRAD_FIELDS, grads[i] if grads is not None else ()):
+            setattr(arr[i], k, x.data_ptr() if x is not None else None)
     return arr
+
+
+def _venc_bytes(prec, R):
+    """view-encoding workspace of a pass over R rays: 32 values per ray in the operand format of `prec`"""
+    return R * 32 * (2 if L.base_prec(prec) == L.PREC_BF16 else 4)
+
+
+def _fill_pass_fwd(*, prec, nrays, nsamp, center, dir, t, noise, noise_scale, white_bg, packed, c2f, save, venc_ws,
+                   raylen, sigma_raw, rgb_samples, density, weights, rgb, depth, opacity, depth_var, rgb_var, all_cumulated):
+    """sparf_pass_fwd_t from addresses (int | None) and scalars: the ONE place that names its fields, all required keywords -- a field
+    a route forgets is a TypeError, not a null pointer.  Segment table and far rows are set on the result (build_pass_fwd, _set_far)."""
+    return L.PassFwd(prec=prec, nrays=nrays, nsamp=nsamp, center=center, dir=dir, t=t, noise=noise, noise_scale=float(noise_scale),
+                     white_bg=int(bool(white_bg)), packed=packed, c2f=c2f, save=save, venc_ws=venc_ws, raylen=raylen, sigma_raw=sigma_raw,
+                     rgb_samples=rgb_samples, density=density, weights=weights, rgb=rgb, depth=depth, opacity=opacity, depth_var=depth_var,
+                     rgb_var=rgb_var, all_cumulated=all_cumulated)
+
+
+def _fill_pass_bwd(*, prec, nrays, nsamp, center, dir, t, noise, noise_scale, white_bg, packed, c2f, tables, save, raylen, sigma_raw,
+                   rgb_samples, weights, ws, grad_params, d_center, d_dir, g_rgb, g_depth, g_opacity, g_weights, g_depth_var, g_rgb_var,
+                   g_all_cumulated, g_density, g_rgb_samples, accumulate_rays=0):
+    """sparf_pass_bwd_t, as _fill_pass_fwd; the nine upstream gradients (_GRAD_FIELDS) are None where an output has none"""
+    return L.PassBwd(prec=prec, nrays=nrays, nsamp=nsamp, center=center, dir=dir, t=t, noise=noise, noise_scale=float(noise_scale),
+                     white_bg=int(bool(white_bg)), packed=packed, c2f=c2f, tables=tables, save=save, raylen=raylen, sigma_raw=sigma_raw,
+                     rgb_samples=rgb_samples, weights=weights, g_rgb=g_rgb, g_depth=g_depth, g_opacity=g_opacity, g_weights=g_weights, ws=ws,
+                     grad_params=grad_params, d_center=d_center, d_dir=d_dir, g_depth_var=g_depth_var, g_rgb_var=g_rgb_var,
+                     g_all_cumulated=g_all_cumulated, g_density=g_density, g_rgb_samples=g_rgb_samples, accumulate_rays=accumulate_rays)
+
+
+def _set_far(a, far, save, prec, R, N, dev):
+    """Far rows of the forward struct `a`: far = (K, far_prec, far_packed) -- the last K samples of every ray also run through far_prec
+    (sparf_hip.h "far rows") -- or (threshold, ...) with a FLOAT threshold: far TILES by value, inference passes only (far_count = -1).
+    save: whether the pass saves for a backward; what the far launch saves is transplanted into the pass's save area by the call, its own
+    area is scratch.  -> what to keep alive until the stream has run the call (the caching allocator hands it out again in stream order)."""
+    k, fprec, fpacked = far
+    far_ws = None
+    if isinstance(k, float):
+        if save or N % 32 != 0:
+            raise L.SparfError("far tiles by value: inference passes with a multiple of 32 samples per ray only")
+        a.far_count, a.far_thr = -1, k
+    else:
+        if not 0 < k < N:
+            raise L.SparfError(f"far rows: 0 < K < samples per ray, got K = {k} of {N}")
+        if save:
+            far_ws = torch.empty(L.load().sparf_save_bytes(fprec, R * k), dtype=torch.uint8, device=dev)
+            a.far_ws = far_ws.data_ptr()
+        a.far_count = int(k)
+    a.far_prec, a.far_packed = int(fprec), fpacked.data_ptr()
+    keep = [fpacked, far_ws]
+    if fprec != prec:              # the view-encoding rows are laid out per precision: the far launch gets its own
+        fvenc = torch.empty(_venc_bytes(fprec, R), dtype=torch.uint8, device=dev)
+        a.far_venc_ws = fvenc.data_ptr()
+        keep.append(fvenc)
+    return keep
 
 
 def build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, segs=None, far=None):
     """Allocate outputs and fill the C struct of sparf_pass_forward.  Returns
     (struct, outputs dict, save buffer(s) or None, scratch list to keep alive).
     segs: optional [(ray0, nrays, noise_scale), ...] ray segments (include/sparf_hip.h sparf_segment_t).
-    far: optional (K, far_prec, far_packed): the last K samples of every ray also run through far_prec (sparf_hip.h "far rows");
-    what that launch saves is transplanted into `save` by the call, its own save area is scratch (kept alive in the returned list
-    until the stream has run the call: the caching allocator hands it out again in stream order)."""
+    far: optional (K | threshold, far_prec, far_packed): far rows (_set_far)."""
     lib = L.load()
     dev = c.device
     R, N = tt.shape
@@ -142,36 +199,18 @@ def build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save,
     out = dict(raylen=f(R), sigma_raw=f(R, N), rgb_samples=f(R, N, 3), density=f(R, N), weights=f(R, N), rgb=f(R, 3),
                depth=f(R), opacity=f(R), depth_var=f(R), rgb_var=f(R), all_cumulated=f(R))
     save_buf = torch.empty(lib.sparf_save_bytes(prec, R * N), dtype=torch.uint8, device=dev) if save else None
-    venc = torch.empty(R * 32 * (2 if L.base_prec(prec) == L.PREC_BF16 else 4), dtype=torch.uint8, device=dev)
-    a = L.PassFwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=tt.data_ptr(),
-                  noise=nz.data_ptr() if nz is not None else None, noise_scale=float(noise_scale), white_bg=int(bool(white_bg)),
-                  packed=packed.data_ptr(), c2f=c2f.data_ptr(), save=save_buf.data_ptr() if save_buf is not None else None, venc_ws=venc.data_ptr(),
-                  **{k: v.data_ptr() for k, v in out.items()})
+    venc = torch.empty(_venc_bytes(prec, R), dtype=torch.uint8, device=dev)
+    a = _fill_pass_fwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=tt.data_ptr(),
+                       noise=nz.data_ptr() if nz is not None else None, noise_scale=noise_scale, white_bg=white_bg, packed=packed.data_ptr(),
+                       c2f=c2f.data_ptr(), save=save_buf.data_ptr() if save_buf is not None else None, venc_ws=venc.data_ptr(),
+                       **{k: v.data_ptr() for k, v in out.items()})
     keep = [venc]
     if segs:
         sa = _segments(segs)
         a.nseg, a.seg = len(segs), sa
         keep.append(sa)
-    if far is not None and isinstance(far[0], float):
-        # far TILES by value: (threshold, far_prec, far_packed); inference passes only (sparf_hip.h far_count = -1)
-        thr, fprec, fpacked = far
-        if save or N % 32 != 0:
-            raise L.SparfError("far tiles by value: inference passes with a multiple of 32 samples per ray only")
-        fvenc = torch.empty(R * 32 * (2 if fprec == L.PREC_BF16 else 4), dtype=torch.uint8, device=dev)
-        a.far_count, a.far_prec, a.far_packed, a.far_thr, a.far_venc_ws = -1, int(fprec), fpacked.data_ptr(), float(thr), fvenc.data_ptr()
-        keep += [fpacked, fvenc]
-    elif far is not None:
-        K, fprec, fpacked = far
-        if not 0 < K < N:
-            raise L.SparfError(f"far rows: 0 < K < samples per ray, got K = {K} of {N}")
-        far_ws = torch.empty(lib.sparf_save_bytes(fprec, R * K), dtype=torch.uint8, device=dev) if save else None
-        a.far_count, a.far_prec, a.far_packed = int(K), int(fprec), fpacked.data_ptr()
-        a.far_ws = far_ws.data_ptr() if far_ws is not None else None
-        if fprec != prec:          # the view-encoding rows are laid out per precision: the far launch gets its own
-            fvenc = torch.empty(R * 32 * (2 if fprec == L.PREC_BF16 else 4), dtype=torch.uint8, device=dev)
-            a.far_venc_ws = fvenc.data_ptr()
-            keep.append(fvenc)
-        keep += [fpacked, far_ws]
+    if far is not None:
+        keep += _set_far(a, far, save, prec, R, N, dev)
     return a, out, save_buf, keep
 
 
@@ -186,20 +225,15 @@ def build_pass_bwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save,
     gp = torch.empty(L.N_PARAMS, dtype=torch.float32, device=dev)
     dc = torch.empty(R, 3, dtype=torch.float32, device=dev) if pose else None
     dd = torch.empty(R, 3, dtype=torch.float32, device=dev) if pose else None
-    if segs:
-        gseg = [[_f32(g) if g is not None else None for g in gt] for gt in grads]
-        gs = [None] * 9
-    else:
-        gs = [_f32(g) if g is not None else None for g in grads]
-        gs += [None] * (9 - len(gs))
+    gseg = [[_f32(g) if g is not None else None for g in gt] for gt in grads] if segs else None
+    gs = [_f32(g) if g is not None else None for g in grads] if not segs else []       # (segmented: the table carries them)
+    gs += [None] * (9 - len(gs))
     tables = L.tables_device(L.base_prec(prec), dev)
     P = lambda x: x.data_ptr() if x is not None else None
-    a = L.PassBwd(prec=prec, nrays=R, nsamp=N, center=P(c), dir=P(d), t=P(tt), noise=P(nz), noise_scale=float(noise_scale),
-                  white_bg=int(bool(white_bg)), packed=P(packed), c2f=P(c2f), tables=P(tables), save=P(save), raylen=P(fwd_out["raylen"]),
-                  sigma_raw=P(fwd_out["sigma_raw"]), rgb_samples=P(fwd_out["rgb_samples"]), weights=P(fwd_out["weights"]),
-                  g_rgb=P(gs[0]), g_depth=P(gs[1]), g_opacity=P(gs[2]), g_weights=P(gs[3]), ws=P(ws), grad_params=P(gp),
-                  d_center=P(dc), d_dir=P(dd), g_depth_var=P(gs[4]), g_rgb_var=P(gs[5]), g_all_cumulated=P(gs[6]), g_density=P(gs[7]),
-                  g_rgb_samples=P(gs[8]))
+    a = _fill_pass_bwd(prec=prec, nrays=R, nsamp=N, center=P(c), dir=P(d), t=P(tt), noise=P(nz), noise_scale=noise_scale, white_bg=white_bg,
+                       packed=P(packed), c2f=P(c2f), tables=P(tables), save=P(save), raylen=P(fwd_out["raylen"]),
+                       sigma_raw=P(fwd_out["sigma_raw"]), rgb_samples=P(fwd_out["rgb_samples"]), weights=P(fwd_out["weights"]), ws=P(ws),
+                       grad_params=P(gp), d_center=P(dc), d_dir=P(dd), **{k: P(g) for k, g in zip(_GRAD_FIELDS, gs)})
     keep = [ws, tables] + gs
     if segs:
         sa = _segments(segs, gseg)
@@ -208,135 +242,104 @@ def build_pass_bwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save,
     return a, gp, dc, dd, keep
 
 
+def _param_grad_views(gp, shapes, needs):
+    """the flat parameter gradient cut into the parameters' shapes: views of it, None where no gradient is wanted"""
+    views, off = [], 0
+    for shp, need in zip(shapes, needs):
+        n = math.prod(shp)
+        views.append(gp[off:off + n].view(shp) if need else None)
+        off += n
+    return views
+
+
 class NerfPass(torch.autograd.Function):
     """One network (coarse or fine) over R rays x N samples: fused MLP + compositing.
 
     Inputs  center [R,3], dirs [R,3], t [R,N], noise [R,N] | None, then the 20 parameter
             tensors (only used to route gradients; the kernels read `packed`).
     Outputs rgb [R,3], depth [R], opacity [R], weights [R,N], depth_var [R], rgb_var [R], all_cumulated [R], density [R,N],
-            rgb_samples [R,N,3] -- ALL differentiable, as in the reference, where NeRF.composite is plain autograd
+            rgb_samples [R,N,3] (PASS_KEYS) -- ALL differentiable, as in the reference, where NeRF.composite is plain autograd
             (frequency_nerf.py:317-338; C ABI 6.  Rounds 1-4 marked the last five non-differentiable: a loss on depth_var
             silently received a zero gradient, VERDICT r04 missing-3).
+    segs    None, or [(ray0, nrays, noise_scale), ...]: the rays of SEVERAL render calls laid back to back, one launch
+            set.  The nine outputs are then returned PER SEGMENT as views of the pass's buffers (no split copies), the upstream gradients
+            consumed per segment through the C ABI's segment table (no gather copies); the noise scales are the table's, `noise_scale`
+            is not used.  (One segment is not the same call as none: the C side then walks the active ray range.)
     """
 
     @staticmethod
-    def forward(ctx, center, dirs, t, noise, noise_scale, white_bg, prec, packed, c2f, grad_mode, far, *params):
+    def forward(ctx, center, dirs, t, noise, noise_scale, white_bg, prec, packed, c2f, grad_mode, far, segs, *params):
         lib = L.load()
         dev = center.device
         L.require_gpu(dev)
         c, d, tt = _f32(center), _f32(dirs), _f32(t)
         nz = _f32(noise) if noise is not None else None
+        noise_scale = 0.0 if segs else float(noise_scale)
         # needs_input_grad ignores the caller's grad mode (and forward() itself always runs with
         # grad disabled): `grad_mode` = torch.is_grad_enabled() at the call site.  Without it
         # nothing is saved and the inference kernel runs.
         need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
         ctx.set_materialize_grads(False)          # absent upstream gradients arrive as None, not as zero tensors
-        a, out, save, _keep = build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, need_grad, far=far)
+        a, out, save, _keep = build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, need_grad, segs=segs, far=far)
         with L.on(dev):
             L.check(lib.sparf_pass_forward(ctypes.byref(a), L.stream_ptr(dev)), "sparf_pass_forward")
         if need_grad:       # (far rows leave nothing of their own behind: their saves were transplanted into `save`)
             ctx.save_for_backward(c, d, tt, nz, packed, c2f, save, out["raylen"], out["sigma_raw"], out["rgb_samples"], out["weights"])
-            ctx.meta = (float(noise_scale), int(bool(white_bg)), prec, [tuple(p.shape) for p in params])
-        return (out["rgb"], out["depth"], out["opacity"], out["weights"], out["depth_var"], out["rgb_var"], out["all_cumulated"],
-                out["density"], out["rgb_samples"])
-
-    @staticmethod
-    def backward(ctx, *g9):
-        lib = L.load()
-        c, d, tt, nz, packed, c2f, save, raylen, sigma_raw, rgb_samples, weights = ctx.saved_tensors
-        noise_scale, white_bg, prec, shapes = ctx.meta
-        pose = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
-        fwd_out = dict(raylen=raylen, sigma_raw=sigma_raw, rgb_samples=rgb_samples, weights=weights)
-        a, gp, dc, dd, _keep = build_pass_bwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, fwd_out, g9, pose)
-        with L.on(c.device):
-            L.check(lib.sparf_pass_backward(ctypes.byref(a), L.stream_ptr(c.device)), "sparf_pass_backward")
-        grads, off = [], 0
-        for i, shp in enumerate(shapes):
-            n = 1
-            for s in shp:
-                n *= s
-            grads.append(gp[off:off + n].view(shp) if ctx.needs_input_grad[11 + i] else None)
-            off += n
-        return (dc if ctx.needs_input_grad[0] else None, dd if ctx.needs_input_grad[1] else None, None, None, None, None, None,
-                None, None, None, None, *grads)
-
-
-class NerfPassSeg(torch.autograd.Function):
-    """NerfPass over the rays of SEVERAL render calls laid back to back: one launch set,
-    the nine outputs returned PER SEGMENT as views of the pass's buffers (no split copies), the upstream
-    gradients consumed per segment through the C ABI's segment table (no gather copies).
-    segs = [(ray0, nrays, noise_scale), ...]; noise: one [R,N] tensor or None."""
-
-    @staticmethod
-    def forward(ctx, center, dirs, t, noise, white_bg, prec, packed, c2f, grad_mode, segs, far, *params):
-        lib = L.load()
-        dev = center.device
-        L.require_gpu(dev)
-        c, d, tt = _f32(center), _f32(dirs), _f32(t)
-        nz = _f32(noise) if noise is not None else None
-        need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
-        ctx.set_materialize_grads(False)
-        a, out, save, _keep = build_pass_fwd(prec, c, d, tt, nz, 0.0, white_bg, packed, c2f, need_grad, segs=segs, far=far)
-        with L.on(dev):
-            L.check(lib.sparf_pass_forward(ctypes.byref(a), L.stream_ptr(dev)), "sparf_pass_forward")
-        if need_grad:
-            ctx.save_for_backward(c, d, tt, nz, packed, c2f, save, out["raylen"], out["sigma_raw"], out["rgb_samples"], out["weights"])
-            ctx.meta = (int(bool(white_bg)), prec, [tuple(p.shape) for p in params], list(segs))
-        keys = ("rgb", "depth", "opacity", "weights", "depth_var", "rgb_var", "all_cumulated", "density", "rgb_samples")
-        res = []
-        for (r0, n, _) in segs:
-            res += [out[k][r0:r0 + n] for k in keys]
-        return tuple(res)
+            ctx.meta = (noise_scale, int(bool(white_bg)), prec, [tuple(p.shape) for p in params], list(segs) if segs else None)
+        whole = [out[k] for k in _PASS_FIELDS]
+        return tuple(x[r0:r0 + n] for (r0, n, _) in segs for x in whole) if segs else tuple(whole)
 
     @staticmethod
     def backward(ctx, *g):
         lib = L.load()
         c, d, tt, nz, packed, c2f, save, raylen, sigma_raw, rgb_samples, weights = ctx.saved_tensors
-        white_bg, prec, shapes, segs = ctx.meta
+        noise_scale, white_bg, prec, shapes, segs = ctx.meta
         pose = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         fwd_out = dict(raylen=raylen, sigma_raw=sigma_raw, rgb_samples=rgb_samples, weights=weights)
-        gseg = [tuple(g[9 * i:9 * i + 9]) for i in range(len(segs))]
-        a, gp, dc, dd, _keep = build_pass_bwd(prec, c, d, tt, nz, 0.0, white_bg, packed, c2f, save, fwd_out, gseg, pose, segs=segs)
+        if segs:
+            g = [g[9 * i:9 * i + 9] for i in range(len(segs))]
+        a, gp, dc, dd, _keep = build_pass_bwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, fwd_out, g, pose, segs=segs)
         with L.on(c.device):
             L.check(lib.sparf_pass_backward(ctypes.byref(a), L.stream_ptr(c.device)), "sparf_pass_backward")
-        grads, off = [], 0
-        for i, shp in enumerate(shapes):
-            n = 1
-            for s in shp:
-                n *= s
-            grads.append(gp[off:off + n].view(shp) if ctx.needs_input_grad[11 + i] else None)
-            off += n
         return (dc if ctx.needs_input_grad[0] else None, dd if ctx.needs_input_grad[1] else None, None, None, None, None, None,
-                None, None, None, None, *grads)
+                None, None, None, None, None, *_param_grad_views(gp, shapes, ctx.needs_input_grad[12:]))
 
 
 def nerf_pass_segments(center, dirs, t, noise, white_bg, prec, packed, c2f, params, segs, far=None):
     """-> list (one per segment) of dicts with the reference's composite keys (flat ray axis)"""
-    flat = NerfPassSeg.apply(center, dirs, t, noise, white_bg, prec, packed, c2f, torch.is_grad_enabled(), list(segs), far, *params)
-    keys = ("rgb", "depth", "opacity", "weights", "depth_var", "rgb_var", "all_cumulated", "density_samples", "rgb_samples")
-    return [dict(zip(keys, flat[9 * i:9 * i + 9])) for i in range(len(segs))]
+    flat = NerfPass.apply(center, dirs, t, noise, 0.0, white_bg, prec, packed, c2f, torch.is_grad_enabled(), far, list(segs), *params)
+    return [dict(zip(PASS_KEYS, flat[9 * i:9 * i + 9])) for i in range(len(segs))]
 
 
 def nerf_pass(center, dirs, t, noise, noise_scale, white_bg, prec, packed, c2f, params, far=None):
     """Convenience wrapper returning a dict with the reference's composite keys (flat ray axis).
     c2f: the pass's band-weight vector (c2f_weights).  far: (K, far_prec, far_packed) or None (build_pass_fwd)."""
-    rgb, depth, opacity, weights, depth_var, rgb_var, all_cum, density, rgb_s = NerfPass.apply(
-        center, dirs, t, noise, noise_scale, white_bg, prec, packed, c2f, torch.is_grad_enabled(), far, *params)
-    return dict(rgb=rgb, depth=depth, opacity=opacity, weights=weights, depth_var=depth_var, rgb_var=rgb_var,
-                all_cumulated=all_cum, density_samples=density, rgb_samples=rgb_s)
+    return dict(zip(PASS_KEYS, NerfPass.apply(center, dirs, t, noise, noise_scale, white_bg, prec, packed, c2f, torch.is_grad_enabled(),
+                                              far, None, *params)))
+
+
+def ray_request(B, pixels, ray_idx, all_rays=None):
+    """(per_image, N, ray_idx) of a request for rays of B poses, without generating them: N rays per image, selected by pixels [N,2] |
+    [B,N,2], else by ray_idx [N] | [B,N], else all `all_rays` = H*W of them.  A 2-D ray_idx whose first dimension is not the batch is
+    one list for every image: it comes back flattened."""
+    if pixels is not None:
+        return int(pixels.dim() == 3), pixels.shape[-2], None
+    if ray_idx is None:
+        return 0, all_rays, None
+    if ray_idx.dim() == 2 and ray_idx.shape[0] != B:
+        ray_idx = ray_idx.reshape(-1)
+    return int(ray_idx.dim() == 2), ray_idx.shape[-1], ray_idx
 
 
 def _ray_sel(pose, pixels, ray_idx):
     """(sel tensor, is_pixels, per_image, N) of a ray-generation request"""
-    B = pose.shape[0]
+    per_image, N, ray_idx = ray_request(pose.shape[0], pixels, ray_idx)
     if pixels is not None:
         sel = _f32(pixels)
-        per_image, N = int(sel.dim() == 3), sel.shape[-2]
+        if per_image and sel.shape[0] != pose.shape[0]:
+            raise ValueError("per-image pixels must have one row per pose")
     else:
         sel = ray_idx.to(device=pose.device, dtype=torch.int64).contiguous()
-        per_image, N = int(sel.dim() == 2), sel.shape[-1]
-    if per_image and sel.shape[0] != B:
-        raise ValueError("per-image pixels / ray_idx must have one row per pose")
     return sel, pixels is not None, per_image, N
 
 
@@ -553,8 +556,7 @@ def composite(ray, density, rgb_samples, t, white_bg):
     if t.requires_grad and torch.is_grad_enabled():
         raise L.SparfError("composite: depth samples that require a gradient are not supported (none of the reference's callers "
                            "differentiates them: renderer.py:323 no_grad, :405-407 fresh draws)")
-    rgb, depth, opacity, weights, depth_var, rgb_var, all_cum = Composite.apply(ray, density, rgb_samples, t, white_bg)
-    return dict(rgb=rgb, depth=depth, opacity=opacity, weights=weights, depth_var=depth_var, rgb_var=rgb_var, all_cumulated=all_cum)
+    return dict(zip(PASS_KEYS[:7], Composite.apply(ray, density, rgb_samples, t, white_bg)))       # (the per-sample two are its inputs)
 
 
 # ---------------------------------------------------------------------------------------------- one render call = one autograd node
@@ -652,27 +654,18 @@ class RenderFn(torch.autograd.Function):
                             "sparf_c2f_weights")
                 c2f_ptr = c2f_off if c2f_off is not None else A(tag + "c2f")
                 if tag == "f":
-                    fn = lib.sparf_sample_fine if u_mid.device.type == "cuda" else lib.sparf_sample_fine_hostgrid
-                    L.check(fn(c_void_p(A("cweights")), c_void_p(A("ct")), L.ptr(u_mid), L.ptr(range_dev), float(cfg["dmin"]), float(cfg["dmax"]),
+                    fn, grid = _fine_grid(lib, u_mid, dev)
+                    L.check(fn(c_void_p(A("cweights")), c_void_p(A("ct")), L.ptr(grid), L.ptr(range_dev), float(cfg["dmin"]), float(cfg["dmax"]),
                                R, Nc, Nf, None, c_void_p(A("ft")), stream), "sparf_sample_fine")
-                bp = L.base_prec(prec)
                 save = torch.empty(lib.sparf_save_bytes(prec, R * N), dtype=torch.uint8, device=dev) if need_grad else None
-                venc = torch.empty(R * 32 * (2 if bp == L.PREC_BF16 else 4), dtype=torch.uint8, device=dev)
+                venc = torch.empty(_venc_bytes(prec, R), dtype=torch.uint8, device=dev)
                 keep.append(venc)
-                a = L.PassFwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=A(tag + "t"),
-                              noise=noise.data_ptr() if noise is not None else None, noise_scale=float(cfg["noise_scale"]) if noise is not None else 0.0,
-                              white_bg=int(cfg["white_bg"]), packed=packed.data_ptr(), c2f=c2f_ptr, save=save.data_ptr() if save is not None else None,
-                              venc_ws=venc.data_ptr(), raylen=A(tag + "raylen"), sigma_raw=A(tag + "sigma_raw"), rgb_samples=A(tag + "rgb_samples"),
-                              density=A(tag + "density"), weights=A(tag + "weights"), rgb=A(tag + "rgb"), depth=A(tag + "depth"), opacity=A(tag + "opacity"),
-                              depth_var=A(tag + "depth_var"), rgb_var=A(tag + "rgb_var"), all_cumulated=A(tag + "all_cumulated"))
+                a = _fill_pass_fwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=A(tag + "t"),
+                                   noise=noise.data_ptr() if noise is not None else None, noise_scale=cfg["noise_scale"] if noise is not None else 0.0,
+                                   white_bg=cfg["white_bg"], packed=packed.data_ptr(), c2f=c2f_ptr, save=save.data_ptr() if save is not None else None,
+                                   venc_ws=venc.data_ptr(), **{k: A(tag + k) for k, _, _ in _PASS_F32[:-1]})        # (all but "t": what the pass writes)
                 if far is not None:
-                    K, fprec = far
-                    far_ws = torch.empty(lib.sparf_save_bytes(fprec, R * K), dtype=torch.uint8, device=dev) if need_grad else None
-                    fvenc = torch.empty(R * 32 * (2 if fprec == L.PREC_BF16 else 4), dtype=torch.uint8, device=dev)
-                    a.far_count, a.far_prec, a.far_packed = int(K), int(fprec), far_packed.data_ptr()
-                    a.far_ws = far_ws.data_ptr() if far_ws is not None else None
-                    a.far_venc_ws = fvenc.data_ptr()
-                    keep += [far_ws, fvenc]
+                    keep += _set_far(a, (far[0], far[1], far_packed), need_grad, prec, R, N, dev)
                 L.check(lib.sparf_pass_forward(ctypes.byref(a), stream), "sparf_pass_forward")
                 saves.append(save)
         # the results: views of the two arenas, one split per arena + one view each
@@ -717,13 +710,12 @@ class RenderFn(torch.autograd.Function):
                 ws = torch.empty(lib.sparf_bwd_workspace_bytes(prec, R, N, int(pose)), dtype=torch.uint8, device=dev)
                 tables = L.tables_device(L.base_prec(prec), dev)
                 P = lambda x: x.data_ptr() if x is not None else None
-                a = L.PassBwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=A(tag + "t"), noise=P(noise),
-                              noise_scale=float(cfg["noise_scale"]) if noise is not None else 0.0, white_bg=int(cfg["white_bg"]), packed=packed.data_ptr(),
-                              c2f=c2f, tables=tables.data_ptr(), save=save.data_ptr(), raylen=A(tag + "raylen"), sigma_raw=A(tag + "sigma_raw"),
-                              rgb_samples=A(tag + "rgb_samples"), weights=A(tag + "weights"), g_rgb=P(gs[0]), g_depth=P(gs[1]), g_opacity=P(gs[2]),
-                              g_weights=P(gs[3]), ws=ws.data_ptr(), grad_params=gp.data_ptr() + (0 if tag == "c" else 4 * L.N_PARAMS),
-                              d_center=P(rays[0]) if pose else None, d_dir=P(rays[1]) if pose else None, g_depth_var=P(gs[4]), g_rgb_var=P(gs[5]),
-                              g_all_cumulated=P(gs[6]), g_density=P(gs[7]), g_rgb_samples=P(gs[8]), accumulate_rays=0 if first else 1)
+                a = _fill_pass_bwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=A(tag + "t"), noise=P(noise),
+                                   noise_scale=cfg["noise_scale"] if noise is not None else 0.0, white_bg=cfg["white_bg"], packed=packed.data_ptr(),
+                                   c2f=c2f, tables=tables.data_ptr(), save=save.data_ptr(), raylen=A(tag + "raylen"), sigma_raw=A(tag + "sigma_raw"),
+                                   rgb_samples=A(tag + "rgb_samples"), weights=A(tag + "weights"), ws=ws.data_ptr(),
+                                   grad_params=gp.data_ptr() + (0 if tag == "c" else 4 * L.N_PARAMS), d_center=P(rays[0]) if pose else None,
+                                   d_dir=P(rays[1]) if pose else None, accumulate_rays=0 if first else 1, **{k: P(x) for k, x in zip(_GRAD_FIELDS, gs)})
                 L.check(lib.sparf_pass_backward(ctypes.byref(a), stream), "sparf_pass_backward")
                 keep += [ws, gs]
                 first = False
@@ -753,9 +745,6 @@ class FlatParams(torch.autograd.Function):
         sizes = [math.prod(s) for s in ctx.shapes]
         parts = g.split_with_sizes(sizes)
         return tuple(x if len(s) == 1 else x.view(s) for x, s in zip(parts, ctx.shapes))
-
-
-RENDER_KEYS = ("rgb", "depth", "opacity", "weights", "depth_var", "rgb_var", "all_cumulated", "density_samples", "rgb_samples", "t")
 
 
 def render_fused(center, dirs, cfg, jitter, u_mid, noise_c, noise_f, range_dev, packed_c, packed_f, far_packed_c, far_packed_f, prog_c, prog_f, theta_c, theta_f):

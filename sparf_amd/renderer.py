@@ -15,8 +15,8 @@ import torch
 from . import camera
 from . import lib as L
 from . import ops
-from .edict import EasyDict as edict
-from .frequency_nerf import FrequencyEmbedder, NeRF, max_rows_per_call, pass_precision
+from .edict import EasyDict as edict, opt_get
+from .frequency_nerf import FrequencyEmbedder, NeRF, max_rows_per_call, pass_precision, shape_pass
 
 
 _LOGGED_MODES = set()
@@ -24,6 +24,11 @@ _LOGGED_MODES = set()
 
 def _as_float(x):
     return float(x.item()) if torch.is_tensor(x) else float(x)
+
+
+def _deterministic(opt, mode):
+    """whether the fine-sampling grid of a render in `mode` is the regular one (renderer.py:326-327)"""
+    return mode not in ['train', 'test-optim'] or (not opt.nerf.sample_stratified)
 
 
 class _Shifted:
@@ -281,18 +286,31 @@ class Graph(torch.nn.Module):
         return float(lo), float(hi), float(np.float32(float(hi) - float(lo))), None
 
     def _fine_gated_off(self, opt, iter):
-        r = getattr(opt.nerf, "ratio_start_fine_sampling_at_x", None) if not hasattr(opt.nerf, "get") \
-            else opt.nerf.get("ratio_start_fine_sampling_at_x", None)
+        r = opt_get(opt.nerf, "ratio_start_fine_sampling_at_x")
         return r is not None and iter is not None and iter < opt.max_iter * r
+
+    def _fine_on(self, opt, iter):
+        """whether the fine pass of a render runs this iteration"""
+        return bool(opt.nerf.fine_sampling) and not self._fine_gated_off(opt, iter)
+
+    def _to_max_fine_off(self, opt, iter):
+        """render_to_max's own, additional gate of its fine pass (renderer.py:574-582)"""
+        s = opt_get(opt.nerf, "start_fine_sampling_at_x")
+        return s is not None and iter is not None and iter < s
+
+    def _slice_step(self, opt, B):
+        """rays per image in one slice of a full-image render: as many as one launch set takes, at least opt.nerf.rand_rays"""
+        n_per_ray = opt.nerf.sample_intvs + (opt.nerf.sample_intvs_fine if opt.nerf.fine_sampling else 0)
+        return max(int(opt.nerf.rand_rays), max_rows_per_call(pass_precision(opt, opt.nerf.sample_intvs)[0], self.device) // max(1, B * n_per_ray))
 
     def _rays(self, opt, pose, H, W, intr, pixels, ray_idx):
         """Ray origins / directions of the selected pixels (renderer.py:273-291).  One fused
         launch (ops.RayGen, with backward to the pose) unless the intrinsics need a gradient or
         `opt.hip.fused_rays` is False, in which case the PyTorch restatement in camera.py runs."""
-        hip = opt.get("hip", None) if hasattr(opt, "get") else getattr(opt, "hip", None)
+        hip = opt_get(opt, "hip")
         fused = (hip is None or hip.get("fused_rays", True)) and not intr.requires_grad
-        if ray_idx is not None and ray_idx.dim() == 2 and ray_idx.shape[0] != len(pose):
-            ray_idx = ray_idx.reshape(-1)
+        if ray_idx is not None:
+            ray_idx = ops.ray_request(len(pose), None, ray_idx)[2]
         if fused:
             if pixels is None and ray_idx is None:
                 ray_idx = torch.arange(H * W, device=pose.device)
@@ -365,17 +383,16 @@ class Graph(torch.nn.Module):
         (`_draw_randoms`): the RNG streams -- and a test harness that injects draws around the call -- see exactly the eager sequence; only
         the kernel launches wait.  A batch is launched by the first read of any of its results, by the next call into the renderer
         that is not deferred, or by the next optimiser step."""
-        hip = opt.get("hip", None) if hasattr(opt, "get") else getattr(opt, "hip", None)
+        hip = opt_get(opt, "hip")
         lazy = (hip is None or hip.get("lazy_batch", True)) if self._lazy_env is None else self._lazy_env != "0"
         if not lazy or (hip is not None and (not hip.get("fused_render", True) or not hip.get("fused_rays", True))) \
                 or mode != "train" or not torch.is_grad_enabled() or opt.camera.ndc or intr.requires_grad:
             return None
         L.require_gpu(pose.device)
         B = pose.shape[0]
-        sel = pixels if pixels is not None else ray_idx
-        R = sel.shape[-2] if pixels is not None else (sel.numel() if (sel.dim() == 2 and sel.shape[0] != B) else sel.shape[-1])
+        R = ops.ray_request(B, pixels, ray_idx, H * W)[1]
         Nc, Nf = int(opt.nerf.sample_intvs), int(opt.nerf.sample_intvs_fine or 0)
-        fine = bool(opt.nerf.fine_sampling) and not self._fine_gated_off(opt, iter)
+        fine = self._fine_on(opt, iter)
         n = B * R
         prec, far = pass_precision(opt, Nc)
         rows = n * (Nc + (Nf if fine else 0))
@@ -404,8 +421,7 @@ class Graph(torch.nn.Module):
         noise_c = torch.randn(n, Nc, device=dev) if use_noise else None                 # frequency_nerf.py:192
         u_mid = noise_f = None
         if fine:
-            det = mode not in ['train', 'test-optim'] or (not opt.nerf.sample_stratified)
-            u_mid = self._grid_midpoints_fused(Nf, det)
+            u_mid = self._grid_midpoints_fused(Nf, _deterministic(opt, mode))
             noise_f = torch.randn(n, Nc + Nf, device=dev) if use_noise else None
         for z in (noise_c, noise_f):
             if z is not None and (z.dtype is not torch.float32 or not z.is_contiguous()):
@@ -462,12 +478,11 @@ class Graph(torch.nn.Module):
         coarse = self.nerf.render_pass(opt, center, ray, depth_samples, mode=mode, n_coarse=Nc)
         coarse["t"] = depth_samples
         pred.update(coarse)
-        if opt.nerf.fine_sampling and not self._fine_gated_off(opt, iter):
+        if self._fine_on(opt, iter):
             Nf = opt.nerf.sample_intvs_fine
-            det = mode not in ['train', 'test-optim'] or (not opt.nerf.sample_stratified)
             dmin, dmax, _, rd = self._range(depth_range)
             with torch.no_grad():
-                u_mid = self._grid_midpoints(Nf, det)
+                u_mid = self._grid_midpoints(Nf, _deterministic(opt, mode))
                 merged, _ = ops.sample_fine(coarse["weights"].view(B * R, Nc), depth_samples.view(B * R, Nc), u_mid, dmin, dmax, range_dev=rd)
             depth_all = merged.view(B, R, Nc + Nf, 1)
             fine = self.nerf_fine.render_pass(opt, center, ray, depth_all, mode=mode, n_coarse=Nc)
@@ -481,12 +496,12 @@ class Graph(torch.nn.Module):
         fine grid, fine density noise: renderer.py:405-407, frequency_nerf.py:191-192, renderer.py:439), same results bit for bit as
         the pass-by-pass path below it (tests/test_graph_gpu.py::test_fused_render_equals_pass_by_pass), which remains for renders
         larger than one launch set and for `opt.hip.fused_render = False`.  -> EasyDict, or None when the pass-by-pass path must run."""
-        hip = opt.get("hip", None) if hasattr(opt, "get") else getattr(opt, "hip", None)
+        hip = opt_get(opt, "hip")
         if hip is not None and not hip.get("fused_render", True):
             return None
         B, R = ray.shape[:2]
         Nc, Nf = int(opt.nerf.sample_intvs), int(opt.nerf.sample_intvs_fine or 0)
-        fine = bool(opt.nerf.fine_sampling) and not self._fine_gated_off(opt, iter)
+        fine = self._fine_on(opt, iter)
         n = B * R
         prec, far = pass_precision(opt, Nc)
         if n == 0 or n * (Nc + (Nf if fine else 0)) > max_rows_per_call(prec, ray.device, need=n * (Nc + (Nf if fine else 0)), far=far):
@@ -511,15 +526,9 @@ class Graph(torch.nn.Module):
             self.nerf.packed(fprec, pc) if far is not None else None, self.nerf_fine.packed(fprec, pf) if (fine and far is not None) else None,
             self.nerf.progress.detach(), self.nerf_fine.progress.detach() if fine else None, theta_c, theta_f)
         pred = edict(origins=center, viewdirs=ray)
-
-        def shaped(o, N):
-            return dict(rgb_samples=o["rgb_samples"].view(B, R, N, 3), density_samples=o["density_samples"].view(B, R, N), rgb=o["rgb"].view(B, R, 3),
-                        rgb_var=o["rgb_var"].view(B, R, 1), depth=o["depth"].view(B, R, 1), depth_var=o["depth_var"].view(B, R, 1),
-                        opacity=o["opacity"].view(B, R, 1), weights=o["weights"].view(B, R, N, 1), all_cumulated=o["all_cumulated"].view(B, R),
-                        t=o["t"].view(B, R, N, 1))
-        pred.update(shaped(coarse, Nc))
+        pred.update(shape_pass(coarse, B, R, Nc), t=coarse["t"].view(B, R, Nc, 1))
         if fine:
-            pred.update({k + "_fine": v for k, v in shaped(fine_out, Nc + Nf).items()})
+            pred.update({k + "_fine": v for k, v in shape_pass(fine_out, B, R, Nc + Nf).items()}, t_fine=fine_out["t"].view(B, R, Nc + Nf, 1))
         return pred
 
     def render_by_slices(self, opt, pose, H, W, intr, depth_range, iter, mode=None):
@@ -527,11 +536,9 @@ class Graph(torch.nn.Module):
         slices to fit 20 GB; here a slice is as large as one kernel launch allows."""
         keys = ["rgb", "rgb_var", "depth", "depth_var", "opacity", "normal", "all_cumulated"]
         ret_all = edict({k: [] for k in keys})
-        if opt.nerf.fine_sampling and not self._fine_gated_off(opt, iter):
+        if self._fine_on(opt, iter):
             ret_all.update({k + "_fine": [] for k in keys})
-        B = len(pose)
-        n_per_ray = opt.nerf.sample_intvs + (opt.nerf.sample_intvs_fine if opt.nerf.fine_sampling else 0)
-        step = max(int(opt.nerf.rand_rays), max_rows_per_call(pass_precision(opt, opt.nerf.sample_intvs)[0], self.device) // max(1, B * n_per_ray))
+        step = self._slice_step(opt, len(pose))
         for c in range(0, H * W, step):
             ray_idx = torch.arange(c, min(c + step, H * W), device=self.device)
             ret = self.render(opt, pose, H=H, W=W, intr=intr, ray_idx=ray_idx, depth_range=depth_range, iter=iter, mode=mode)
@@ -551,9 +558,8 @@ class Graph(torch.nn.Module):
         reference's `MSE_loss` of the whole batch)."""
         B = len(pose)
         target = image.reshape(B, 3, H * W).permute(0, 2, 1) if image.dim() == 4 else image.reshape(B, H * W, 3)
-        fine = opt.nerf.fine_sampling and not self._fine_gated_off(opt, iter)
-        n_per_ray = opt.nerf.sample_intvs + (opt.nerf.sample_intvs_fine if opt.nerf.fine_sampling else 0)
-        step = max(int(opt.nerf.rand_rays), max_rows_per_call(pass_precision(opt, opt.nerf.sample_intvs)[0], self.device) // max(1, B * n_per_ray))
+        fine = self._fine_on(opt, iter)
+        step = self._slice_step(opt, B)
         sq = torch.zeros(2, device=self.device, dtype=torch.float64)
         for c in range(0, H * W, step):
             hi = min(c + step, H * W)
@@ -591,7 +597,7 @@ class Graph(torch.nn.Module):
         """the mid-points for the fused render: a HOST float32 tensor where the grid is drawn on the CPU as the reference does
         (renderer.py:439) and fits the launch arguments (C ABI sparf_sample_fine_hostgrid: no host -> device copy at all), else the
         device tensor of _grid_midpoints"""
-        hip = self.opt.get("hip", None) if hasattr(self.opt, "get") else None
+        hip = opt_get(self.opt, "hip")
         if det or n_fine > 256 or (hip is not None and hip.get("device_rng", False)):
             return self._grid_midpoints(n_fine, det)
         cpu = torch.rand(n_fine + 1)
@@ -611,7 +617,7 @@ class Graph(torch.nn.Module):
         # one shared, unsorted draw made on the CPU, as the reference does (renderer.py:439),
         # but staged through a small ring of pinned buffers: a pageable .to(device) would
         # block the host behind everything already queued on the stream, every step
-        hip = self.opt.get("hip", None) if hasattr(self.opt, "get") else None
+        hip = opt_get(self.opt, "hip")
         if hip is not None and hip.get("device_rng", False):
             # opt.hip.device_rng: draw on the device instead (same distribution, different
             # RNG stream) -- keeps the whole step free of host->device copies, which is
@@ -669,11 +675,7 @@ class Graph(torch.nn.Module):
         coarse = self.nerf.render_pass(opt, center, ray, depth_samples, mode=mode, to_max=True)
         coarse["t"] = depth_samples
         pred.update(coarse)
-        skip = self._fine_gated_off(opt, iter)
-        s = getattr(opt.nerf, "start_fine_sampling_at_x", None) if not hasattr(opt.nerf, "get") else opt.nerf.get("start_fine_sampling_at_x", None)
-        if not skip and s is not None and iter is not None and iter < s:
-            skip = True
-        if opt.nerf.fine_sampling and not skip:
+        if self._fine_on(opt, iter) and not self._to_max_fine_off(opt, iter):
             fine = self.nerf_fine.render_pass(opt, center, ray, depth_samples, mode=mode, to_max=True)
             fine["t"] = depth_samples
             pred.update({k + "_fine": v for k, v in fine.items()})
@@ -708,25 +710,15 @@ class Graph(torch.nn.Module):
         Nf = opt.nerf.sample_intvs_fine
         reg = float(opt.nerf.density_noise_reg) if opt.nerf.density_noise_reg else 0.0
         dev = self.device
-        fine_on = bool(opt.nerf.fine_sampling) and not self._fine_gated_off(opt, iter)
-        s0 = opt.nerf.get("start_fine_sampling_at_x", None) if hasattr(opt.nerf, "get") else getattr(opt.nerf, "start_fine_sampling_at_x", None)
-        tomax_skip = s0 is not None and iter is not None and iter < s0
+        fine_on = self._fine_on(opt, iter)
+        tomax_skip = self._to_max_fine_off(opt, iter)
         white_bg = bool(opt.nerf.setbg_opaque or opt.mask_img)
-
-        def count(q):
-            """rays of a request without generating them: B * (pixels | ray_idx rows | H*W)"""
-            B = q["pose"].shape[0]
-            sel = q.get("pixels") if q.get("pixels") is not None else q.get("ray_idx")
-            if sel is None:
-                return B, q["H"] * q["W"]
-            if q.get("pixels") is None and sel.dim() == 2 and sel.shape[0] != B:
-                return B, sel.numel()
-            return B, sel.shape[-2] if q.get("pixels") is not None else sel.shape[-1]
 
         items = []
         for q in requests:
             q = dict(q)
-            B, R = count(q)
+            B = q["pose"].shape[0]
+            R = ops.ray_request(B, q.get("pixels"), q.get("ray_idx"), q["H"] * q["W"])[1]
             items.append(dict(q=q, mode=q.get("mode"), to_max="depth_max" in q, B=B, R=R, n=B * R,
                               nograd=bool(q.get("no_grad", False)) or not torch.is_grad_enabled()))
 
@@ -742,7 +734,7 @@ class Graph(torch.nn.Module):
             Rtot = sum(m["n"] for m in members)
             with torch.set_grad_enabled(not nograd):
                 # ray generation of the whole group into one (centres, directions) buffer, each request at its offset
-                hip = opt.get("hip", None) if hasattr(opt, "get") else getattr(opt, "hip", None)
+                hip = opt_get(opt, "hip")
                 # (pixel lists that carry a gradient -- depth_cons_loss.py:291 -- take the per-request path: ops.RayGenMany sees its
                 # pixel lists as plain data)
                 fused = (hip is None or hip.get("fused_rays", True)) and not any(
@@ -755,8 +747,6 @@ class Graph(torch.nn.Module):
                     px, ix = q.get("pixels"), q.get("ray_idx")
                     if px is None and ix is None:
                         ix = torch.arange(q["H"] * q["W"], device=dev)
-                    if ix is not None and ix.dim() == 2 and ix.shape[0] != m["B"]:
-                        ix = ix.reshape(-1)
                     specs.append((q["intr"], px, None if px is not None else ix, q["W"]))
                 if opt.camera.ndc:
                     raise NotImplementedError("camera.ndc is dead code in the reference (renderer.py:295 vs camera.py:439) and unsupported here")
@@ -814,11 +804,7 @@ class Graph(torch.nn.Module):
                     outs = ops.nerf_pass_segments(rays[0, lo:hi], rays[1, lo:hi], t_buf[lo:hi], noise, white_bg, prec, net.packed(prec),
                                                   net.band_weights(), net.hip_params(), segs, far=far)
                     for m, o in zip(group, outs):
-                        B, R = m["B"], m["R"]
-                        part = dict(rgb_samples=o["rgb_samples"].view(B, R, N, 3), density_samples=o["density_samples"].view(B, R, N),
-                                    rgb=o["rgb"].view(B, R, 3), rgb_var=o["rgb_var"].view(B, R, 1), depth=o["depth"].view(B, R, 1),
-                                    depth_var=o["depth_var"].view(B, R, 1), opacity=o["opacity"].view(B, R, 1),
-                                    weights=o["weights"].view(B, R, N, 1), all_cumulated=o["all_cumulated"].view(B, R), t=m[key_t])
+                        part = dict(shape_pass(o, m["B"], m["R"], N), t=m[key_t])
                         m["out" + suffix] = part
                         m["pred"].update({k + suffix: v for k, v in part.items()})
 
@@ -832,7 +818,7 @@ class Graph(torch.nn.Module):
                         lo = rend[0]["off"]
                         t_fine = torch.empty(sum(m["n"] for m in rend), Nc + Nf, device=dev, dtype=torch.float32)
                         for m in rend:
-                            det = m["mode"] not in ['train', 'test-optim'] or (not opt.nerf.sample_stratified)
+                            det = _deterministic(opt, m["mode"])
                             dmin, dmax, _, rd = self._range(m["q"]["depth_range"])
                             tv = t_fine[m["off"] - lo:m["off"] - lo + m["n"]]
                             if m["n"] > 0:

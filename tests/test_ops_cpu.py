@@ -133,3 +133,56 @@ def test_pending_render_reads_launch_and_writes_do_not():
         a = b.add()
         d = dup(a)
         assert b.flushed == 1 and type(d) is edict and float(d.rgb[0]) == 0.0 and not isinstance(d, PendingRender)
+
+
+def test_struct_fillers_put_every_address_under_its_own_name():
+    """ops._fill_pass_fwd / _fill_pass_bwd are the only code that names the fields of sparf_pass_fwd_t / sparf_pass_bwd_t.  A pointer
+    stored under a neighbour's name or left out does not crash: the kernels read the wrong buffer, or take null for "not wanted" and
+    return a zero gradient (VERDICT r04 missing-3).  Every argument gets an address of its own; every field must read it back, and
+    what a filler is not given (segment table, far rows, optional gradients) must stay null / zero."""
+    import ctypes
+    import inspect
+    for fill, struct, optional in ((ops._fill_pass_fwd, L.PassFwd, ()), (ops._fill_pass_bwd, L.PassBwd, ("accumulate_rays",))):
+        ctype = dict(struct._fields_)
+        sig = inspect.signature(fill).parameters
+        assert all(p.kind is p.KEYWORD_ONLY for p in sig.values())              # no positional argument to transpose
+        assert {n for n, p in sig.items() if p.default is not p.empty} == set(optional)     # forgetting any other field is a TypeError
+        pointers = [n for n in sig if ctype[n] is ctypes.c_void_p]
+        given = {n: 0x1000 * (i + 1) for i, n in enumerate(pointers)}
+        given.update(prec=L.PREC_X3 | L.SAVE_Q8, nrays=37, nsamp=192, noise_scale=0.25, white_bg=True)
+        if "accumulate_rays" in sig:
+            given["accumulate_rays"] = 1
+        assert set(given) == set(sig)
+        a = fill(**given)
+        for n in pointers:
+            assert getattr(a, n) == given[n], n
+        assert (a.prec, a.nrays, a.nsamp, a.noise_scale, a.white_bg) == (L.PREC_X3 | L.SAVE_Q8, 37, 192, 0.25, 1)
+        for n in ctype:
+            if n not in sig:                                                     # nseg / seg, the far-row fields
+                v = getattr(a, n)
+                assert not v if n == "seg" else v in (None, 0, 0.0), n
+        with pytest.raises(TypeError):
+            fill(**{k: v for k, v in given.items() if k != "weights"})
+        # the optional ones, left out: null
+        b = fill(**{k: v for k, v in given.items() if k not in optional})
+        for n in optional:
+            assert getattr(b, n) in (None, 0), n
+        # None is a null pointer
+        assert fill(**dict(given, noise=None)).noise is None
+    # the name tuple the routes expand the upstream gradients into; a short list of them is a TypeError, not null pointers
+    assert ops._GRAD_FIELDS == tuple(n for n, _ in L.PassBwd._fields_ if n.startswith("g_"))
+    with pytest.raises(TypeError):
+        ops._fill_pass_bwd(**{k: v for k, v in given.items() if k not in ops._GRAD_FIELDS[4:]})
+    fwd = [n for n, _ in L.PassFwd._fields_]
+    assert {n for n, _, _ in ops._PASS_F32[:-1]} == set(fwd[fwd.index("venc_ws") + 1:fwd.index("nseg")])
+
+
+def test_ray_request_counts_rays_and_flattens_a_ray_idx_that_is_not_per_image():
+    """ops.ray_request, the one statement of how many rays per image a request selects (Graph's deferred and batched routes size
+    their buffers with it before any ray exists; ops.RayGen reads the same answer)"""
+    px, idx = torch.zeros(5, 2), torch.arange(12)
+    assert ops.ray_request(3, px, None)[:2] == (0, 5) and ops.ray_request(3, px.expand(3, 5, 2), idx)[:2] == (1, 5)
+    assert ops.ray_request(3, None, idx)[:2] == (0, 12) and ops.ray_request(3, None, idx.view(3, 4))[:2] == (1, 4)
+    per_image, n, flat = ops.ray_request(3, None, idx.view(2, 6))           # two rows, three poses: one list of 12 for every image
+    assert (per_image, n) == (0, 12) and torch.equal(flat, idx)
+    assert ops.ray_request(3, None, None, 30 * 40) == (0, 1200, None)
