@@ -139,7 +139,7 @@ struct BwdWs {
 // others to prec; needs nsamp % 32 == 0 (a 32-row wave tile then lies inside one ray, whose samples increase)
 static inline bool far_ok(int far_count, int far_prec, int nsamp, int prec) {
     if (far_count == 0) return true;
-    if (far_prec != PREC_FP32 || prec == PREC_FP32 || nplanes_of(prec) != 1) return false;
+    if (far_prec != PREC_FP32 || prec == PREC_FP32) return false;
     // tile routing decides per WORKGROUP tile (nwaves x 32 rows): both launches must cut the rows into the same tiles, or a tile of
     // the wider kernel that straddles the threshold would be skipped by it and only half-evaluated by the other (the
     // 8-wave bf16 kernels against the 4-wave fp32 far kernel; bf16x3 runs 4 waves)

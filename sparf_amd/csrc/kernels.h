@@ -66,11 +66,8 @@ struct WgradArgs {
     float* partial;            // [nsplit][wpartial_floats()]
     int64_t row_begin;         // first active row (multiple of 32)
 };
-// accumulate: grad_out += the reduced partials (the far launch of a routed pass, after the main one wrote grad_out)
-int launch_wgrad(int prec, bool q8, const WgradArgs& a, int nsplit, const int32_t* wsrc, float* grad_out, hipStream_t s, bool accumulate = false);
-// the two halves of launch_wgrad, for the chunked dgrad || wgrad schedule of sparf_pass_backward (api.hip)
-int launch_wgrad_partials(int prec, bool q8, const WgradArgs& a, int nsplit, hipStream_t s);
-int launch_wgrad_reduce(const float* partial, int nsplit, const int32_t* wsrc, float* grad_out, hipStream_t s, bool accumulate);
+// split-K partials of `nsplit` row ranges, then grad_out = their sum in nn.Linear order (wsrc: tables.cpp)
+int launch_wgrad(int prec, bool q8, const WgradArgs& a, int nsplit, const int32_t* wsrc, float* grad_out, hipStream_t s);
 
 // ray segments of a pass (include/sparf_hip.h sparf_segment_t), by value in the kernel arguments.  Read with
 // compile-time indices only (an unrolled select chain): a kernel-argument array indexed with a run-time value

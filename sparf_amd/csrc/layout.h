@@ -30,8 +30,8 @@ namespace sparf {
 // Precision modes.  PREC_X3 ("bf16x3"): every fp32 operand is split into a bf16 head and a
 // bf16 tail (x = hi + lo, 16 mantissa bits) and a product is three bf16 MFMAs
 // (hi*hi + hi*lo + lo*hi, fp32 accumulate): bf16-MFMA rate / 3 at ~2e-5 relative error.  It
-// shares the bf16 register / fragment layout (KJ = 8); its saved activations are two bf16
-// planes (all heads, then all tails), its weight fragments are [1 KiB heads][1 KiB tails].
+// shares the bf16 register / fragment layout (KJ = 8); its saved activations are the bf16
+// head plane (below), its weight fragments are [1 KiB heads][1 KiB tails].
 enum { PREC_BF16 = 0, PREC_FP32 = 1, PREC_X3 = 2, N_PREC = 3 };
 
 // ---- C-row <-> (q, h) ---------------------------------------------------------------
@@ -51,14 +51,11 @@ SP_HD constexpr int kj_of(int prec) { return prec == PREC_FP32 ? 1 : 8; }
 SP_HD constexpr int ch_of(int prec) { return prec == PREC_FP32 ? 4 : 8; }
 // bytes per logical element of a weight stream (x3: head + tail)
 SP_HD constexpr int abytes_of(int prec) { return prec == PREC_BF16 ? 2 : 4; }
-// Saved activations / gradients (the wgrad operands).  bf16x3 keeps only the HEAD plane by
-// default: the weight gradient is a sum over rows of products of already-computed values, its
+// Saved activations / gradients (the wgrad operands).  bf16x3 keeps only the HEAD plane:
+// the weight gradient is a sum over rows of products of already-computed values, its
 // operands' bf16 rounding is unbiased and averages out (relative error ~ 2^-8 / sqrt(rows), far
 // below the ReLU-flip noise of the mode), whereas the forward and data-gradient chains, which
-// propagate errors, keep all three partial products.  -DSP_X3_SAVE_PLANES=2 stores the tails too.
-#ifndef SP_X3_SAVE_PLANES
-#define SP_X3_SAVE_PLANES 1
-#endif
+// propagate errors, keep all three partial products.  (Round 2's build that stored the tails too: code retired, last in ebe6c54.)
 // AREA FORMATS.  The save / gradient areas of a pass are laid out per "area format" af: a precision id (planes of that
 // precision's element type, as above) or AREA_Q8 -- the 8-bit format of the bf16-operand modes (sparf_hip.h SPARF_SAVE_Q8):
 // every saved vector of a row as signed 8-bit integers on a LINEAR grid with one fp32 step per row and vector,
@@ -68,10 +65,7 @@ SP_HD constexpr int abytes_of(int prec) { return prec == PREC_BF16 ? 2 : 4; }
 // area takes an area format.
 enum { AREA_Q8 = 3 };
 SP_HD constexpr int area_format(int prec, bool q8) { return q8 ? (int)AREA_Q8 : prec; }
-SP_HD constexpr int nplanes_of(int prec) { return prec == PREC_X3 ? SP_X3_SAVE_PLANES : 1; }
 SP_HD constexpr int plane_ebytes_of(int prec) { return prec == PREC_FP32 ? 4 : prec == AREA_Q8 ? 1 : 2; }
-// bytes per logical element of a saved row (all planes)
-SP_HD constexpr int save_abytes_of(int prec) { return nplanes_of(prec) * plane_ebytes_of(prec); }
 SP_HD constexpr int frag_bytes_of(int prec) { return prec == PREC_BF16 ? 1024 : prec == PREC_FP32 ? 256 : 2048; }
 
 // column of (q,h) inside a saved activation row: lanes write 16-byte chunks, the two
@@ -167,8 +161,8 @@ SP_HD constexpr int64_t grad_coloff(int b) {
 }
 // AREAS.  The save area (forward -> dgrad / wgrad) and the gradient area (dgrad -> wgrad) are
 // TILE-BLOCK-major: everything a 32-row tile owns is one contiguous block,
-//     save area : [tile32][plane][buffer b][16-byte chunk c][row&31][CH elements] ... then SB_COUNT mask KiB
-//     grad area : [tile32][plane][buffer b][16-byte chunk c][row&31][CH elements]
+//     save area : [tile32][buffer b][16-byte chunk c][row&31][CH elements] ... then SB_COUNT mask KiB
+//     grad area : [tile32][buffer b][16-byte chunk c][row&31][CH elements]
 // i.e. inside a buffer exactly the register image of a wave (32 rows x CH-element chunks): every
 // 16-byte store / load instruction of the fused kernels covers 1 KiB of contiguous memory, and a
 // 32-row x C-column operand tile of the wgrad kernel is one contiguous block.  A wave addresses its
@@ -199,13 +193,13 @@ enum { Q8_STEP_BYTES = 2 * 32 * 4 };        // per buffer and tile
 SP_HD constexpr int64_t save_plane_tile_bytes(int af) { return (int64_t)SAVE_COLS * 32 * plane_ebytes_of(af); }
 SP_HD constexpr int64_t grad_plane_tile_bytes(int af) { return (int64_t)GRAD_COLS * 32 * plane_ebytes_of(af); }
 SP_HD constexpr int64_t save_tile_bytes(int af) {
-    return nplanes_of(af) * save_plane_tile_bytes(af) + SB_COUNT * MASK_TILE_BYTES + (af == AREA_Q8 ? SB_COUNT * Q8_STEP_BYTES : 0);
+    return save_plane_tile_bytes(af) + SB_COUNT * MASK_TILE_BYTES + (af == AREA_Q8 ? SB_COUNT * Q8_STEP_BYTES : 0);
 }
-SP_HD constexpr int64_t grad_tile_bytes(int af) { return nplanes_of(af) * grad_plane_tile_bytes(af) + (af == AREA_Q8 ? GB_COUNT * Q8_STEP_BYTES : 0); }
-// byte offsets inside a tile block: buffer b (head plane), its mask KiB, its steps (AREA_Q8)
+SP_HD constexpr int64_t grad_tile_bytes(int af) { return grad_plane_tile_bytes(af) + (af == AREA_Q8 ? GB_COUNT * Q8_STEP_BYTES : 0); }
+// byte offsets inside a tile block: buffer b, its mask KiB, its steps (AREA_Q8)
 SP_HD constexpr int save_buf_tile_off(int af, int b) { return (int)(save_coloff(b) * 32 * plane_ebytes_of(af)); }
 SP_HD constexpr int grad_buf_tile_off(int af, int b) { return (int)(grad_coloff(b) * 32 * plane_ebytes_of(af)); }
-SP_HD constexpr int save_mask_tile_off(int af, int b) { return (int)(nplanes_of(af) * save_plane_tile_bytes(af)) + b * MASK_TILE_BYTES; }
+SP_HD constexpr int save_mask_tile_off(int af, int b) { return (int)save_plane_tile_bytes(af) + b * MASK_TILE_BYTES; }
 SP_HD constexpr int save_step_tile_off(int b, int part) { return save_mask_tile_off(AREA_Q8, SB_COUNT) + b * Q8_STEP_BYTES + part * 128; }
 SP_HD constexpr int grad_step_tile_off(int b, int part) { return (int)grad_plane_tile_bytes(AREA_Q8) + b * Q8_STEP_BYTES + part * 128; }
 SP_HD constexpr int64_t save_area_bytes(int af, int64_t rows) { return ntiles32(rows) * save_tile_bytes(af); }

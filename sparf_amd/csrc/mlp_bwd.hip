@@ -15,12 +15,7 @@ int launch_mlp_bwd(int prec, bool pose, bool q8, const MlpBwdArgs& a, int grid, 
     if (a.rows <= 0) return 0;
     if (q8) return launch_mlp_bwd_q8(prec, pose, a, grid, stream);
     if (prec == PREC_FP32) return launch_mlp_bwd_fp32(pose, a, grid, stream);
-    if (prec == PREC_X3) {
-#if SP_X3_DGRAD_WAVES
-        waves = SP_X3_DGRAD_WAVES;
-#endif
-        return waves == 4 ? launch_mlp_bwd_x3w4(pose, a, grid, stream) : launch_mlp_bwd_x3(pose, a, grid, stream);
-    }
+    if (prec == PREC_X3) return waves == 4 ? launch_mlp_bwd_x3w4(pose, a, grid, stream) : launch_mlp_bwd_x3(pose, a, grid, stream);
     if (prec != PREC_BF16) return 1;
     if (pose) hipLaunchKernelGGL((mlp_bwd_kernel<PREC_BF16, true>), dim3(grid), dim3(Policy<PREC_BF16>::NWAVES * 64), 0, stream, a);
     else hipLaunchKernelGGL((mlp_bwd_kernel<PREC_BF16, false>), dim3(grid), dim3(Policy<PREC_BF16>::NWAVES * 64), 0, stream, a);

@@ -27,24 +27,13 @@ static __device__ unsigned long long g_prof_bwd[10];
 // `pre(g)` runs right after the group's first chunk barrier (group 0 loads the layer's ReLU
 // mask words there), then `store(g, ngroups)` issues this group's slice of the layer's dY
 // stores: a short burst while the wave waits for its first LDS fragments (mlp_dev.h).
-// SP_BWD_SPREAD: the next chunk's weight-DMA pieces are issued one at a time between the MFMAs of the current chunk (mlp_dev.h
+// Spread weight fetch: the next chunk's weight-DMA pieces are issued one at a time between the MFMAs of the current chunk (mlp_dev.h
 // SpreadFetch) instead of as a burst behind the chunk barrier, where all eight waves queue up at the CU's one vector-memory
 // port (~570 cycles per 32 KiB chunk at the 58 B/clk an LDS-DMA stream reaches) with the matrix pipe idle.
-// 0 = burst everywhere (rounds 1-4), 1 = spread in the kernels WITHOUT pose gradients (default), 2 = spread everywhere.
+// Spread in the kernels WITHOUT pose gradients and in the 4-wave kernel; the 8-wave pose kernels keep the burst (rounds 1-4: burst everywhere).
 // Same-box A/B, 786 432 rows, two repetitions (profiles/r05_kernel_ab_spread.log): dgrad bf16 0.916 / 0.908 -> 0.873 / 0.868 ms (-4.5 %),
 // bf16x3 1.381 / 1.350 -> 1.339 / 1.333 (-2 %), bf16x3 with 8-bit areas 1.311 / 1.305 -> 1.275 / 1.289 (-2 %); the pose variants, which sit
 // at the 256-VGPR limit, spill 9-10 registers with it and measure 1.470 / 1.453 -> 1.481 / 1.469: they keep the burst.
-#ifndef SP_BWD_SPREAD
-#define SP_BWD_SPREAD 1
-#endif
-// SP_BWD_DEFER: 1 = the kernels with bf16 gradient operands double-buffer their accumulators and issue a group's mask epilogue behind the
-// next group's MFMAs (bwd_layer_deferred below; default), 0 = group by group (rounds 1-4).
-#ifndef SP_BWD_DEFER
-#define SP_BWD_DEFER 1
-#endif
-#ifndef SP_BWD_STAGGER
-#define SP_BWD_STAGGER 0
-#endif
 // timing probes (WRONG RESULTS; tools/evidence.sh dgradprobes): SP_PROBE_NO_DMA = the weight chunks are fetched once, every later chunk
 // re-reads what the first left in LDS (mlp_dev.h SP_PROBE_NBYTES); SP_PROBE_NO_STORES = no gradient-area stores; SP_PROBE_NO_BARRIER = no
 // chunk barriers (with NO_DMA).  What is left of a wave's barrier waits without them is the SIMD's other wave using the matrix pipe.
@@ -70,20 +59,21 @@ SP_DEV void bwd_group(Pipe& pipe, int lane, const typename P::B* dy, f32x16 (&ac
     });
 }
 
-// Deferred mask epilogue (SP_BWD_DEFER, the default since round 5; every kernel with bf16 gradient operands): the accumulators are
+// Deferred mask epilogue (the default since round 5; every kernel with bf16 gradient operands; fp32 goes group by group): the accumulators are
 // double-buffered and group g-1's epilogue -- BWD_EPI_STAGES units per register pair, `epi(mb, pair, stage, acc)` -- is issued one
 // unit per gap behind group g's MFMAs (mlp_dev.h DeferredEpi; with two partial products per k-step the units take the first
 // part's gaps, the fragment reads and DMA pieces the second's).  Only the segment's last group keeps an exposed epilogue.
 // Round 4 had ruled this out for the 8-wave kernels by register count (244-254 of 256 in use); compiled, it needs 238-252 and no
-// scratch (tools/kernel_meta.sh) -- the epilogue's temporaries no longer overlap a full group of live fragments.
+// scratch (tools/kernel_stream.py) -- the epilogue's temporaries no longer overlap a full group of live fragments.
 // Same box, 786 432 rows, two repetitions, results bit-identical (profiles/r05_kernel_ab_dgrad_defer{,_bf16}.log, r05_dgrad_defer_digests.log):
 //   bf16x3  dgrad 1.338-1.357 -> 1.307-1.318 ms   8-bit areas 1.302-1.304 -> 1.260-1.269   with pose gradients 1.469-1.486 -> 1.458-1.467
 //   bf16          0.880-0.897 -> 0.852                        0.842-0.847 -> 0.811-0.814                       1.010-1.024 -> 0.977-0.991
 // i.e. -2.5 ... -4 %, although the exposed epilogues were 9.3 % of a wave's cycles (wave-time accounting, profiles/r05_dgrad_lap_table.log:
 // epilogue 9.3 % -> 1.8 %, the wave's total -7 %): with two waves per SIMD the other wave's MFMAs already filled most of that time.
-// The 4-wave variant (-DSP_X3_DGRAD_WAVES=4: one wave per SIMD, 128-row tiles, the forward's geometry) with the same deferral:
+// The 4-wave variant (round 5: a build flag, code retired, last in ebe6c54; since round 6 mlp_bwd_x3w4.hip: one wave per SIMD, 128-row tiles, the forward's geometry) with the same deferral:
 // 1.49-1.59 ms, 12-17 % SLOWER than the 8-wave kernel -- twice the weight-stream traffic per row and nobody to issue while the
-// wave queues at the vector-memory port.  Kept as a build flag.
+// wave queues at the vector-memory port.
+// Store bursts of a SIMD's two waves behind different chunk barriers: measured, not adopted (HISTORY round 5 (v); code retired, last in ebe6c54).
 // What the timing probes below say about the rest (pose kernel, same log): no stores 1.551 -> 1.267 ms, no weight DMA -> 1.385, neither
 // -> 1.158, and without the chunk barriers as well 1.136: the barriers themselves are 2 %, the 36 % "barrier" share of a wave's cycles
 // is the SIMD's other wave using the matrix pipe, and what the kernel pays for is its vector-memory traffic -- the gradient stores
@@ -116,18 +106,10 @@ SP_DEV void bwd_layer_deferred(Pipe& pipe, int lane, const typename P::B* dy, Ep
             constexpr int noff = (int)bwd_chunk_off(PREC, nxt);
             constexpr int nbytes = SP_PROBE_NBYTES(chunk_bytes(PREC, bwd_chunk(PREC, nxt)));
             const char* ch = pipe.template acquire<noff, nbytes>();
-            // SP_BWD_STAGGER (experiment, off): the two waves of a SIMD (w, w + 4) issue their store bursts behind DIFFERENT chunk barriers of
-            // the group, so that one of them keeps the matrix pipe fed while the other queues at the CU's vector-memory port.  Bit-identical;
-            // bf16x3 dgrad 1.332-1.336 -> 1.321-1.338 ms, 8-bit areas 1.285 -> 1.256-1.265, with pose gradients 1.483-1.486 -> 1.477-1.493 and 12
-            // spilled registers (profiles/r05_kernel_ab_dgrad_final.log): the stores' price is not their collision at the port.
-            constexpr bool STAG = SP_BWD_STAGGER && bwd_nparts(PREC, L) >= 2 && P::NWAVES == 8;
             if constexpr (part == 0) {
                 pre(gc);
-                if (!STAG || pipe.wave < 4) store(gc, std::integral_constant<int, NG>{});
+                store(gc, std::integral_constant<int, NG>{});
                 zero_acc<P, nmb>(acc);
-            }
-            if constexpr (part == 1 && STAG) {
-                if (pipe.wave >= 4) store(gc, std::integral_constant<int, NG>{});
             }
             SP_LAP(pipe.prof, 4);
             if constexpr (g > 0) {
@@ -171,7 +153,7 @@ __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
     float* c2f = (float*)(lds + PIPE_LDS_BYTES + DX_BYTES);      // the ten position-band weights of the pass, read per lane by the encoding backward
     if (POSE && threadIdx.x < 10) c2f[threadIdx.x] = a.c2f[threadIdx.x];             // (visible after the first chunk barrier)
 
-    WeightPipe<NW, (SP_BWD_SPREAD == 2 || (SP_BWD_SPREAD == 1 && (!POSE || NW == 4)))> pipe;
+    WeightPipe<NW, (!POSE || NW == 4)> pipe;
     pipe.init(a.packed + BWD_OFF, BWD_BYTES, lds);
     pipe.prime(0, C0_BYTES);
 #ifdef SP_PROBE_NO_DMA
@@ -222,7 +204,7 @@ __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
                     constexpr int c0 = g * NST / ng, c1 = (g + 1) * NST / ng;
                     constexpr int BASE = grad_buf_tile_off(AF, gb) + (col0 / CH) * 512;
                     if constexpr (c1 > c0)
-                        static_for<c1 - c0>([&](auto cc) { bstore_chunk<P, BASE, c0 + decltype(cc)::value, (int)grad_plane_tile_bytes(AF)>(grs, lvo, v); });
+                        static_for<c1 - c0>([&](auto cc) { bstore_chunk<P, BASE, c0 + decltype(cc)::value>(grs, lvo, v); });
                 }
             };
         };
@@ -238,7 +220,7 @@ __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
         auto masks_of = [&](auto sbc, unsigned* mk, auto nmc) {
             return [&srs, lane, mk](auto gc) {
                 if constexpr (decltype(gc)::value == 0) {
-                    const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(srs, lane * 16, save_mask_tile_off(AF, decltype(sbc)::value), SP_SAVE_AUX);
+                    const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(srs, lane * 16, save_mask_tile_off(AF, decltype(sbc)::value), SAVE_AUX);
 #pragma unroll
                     for (int p = 0; p < decltype(nmc)::value / 2; ++p) mk[p] = w[p];
                 }
@@ -303,7 +285,7 @@ __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
                 }
             };
         };
-        constexpr bool DEFER = SP_BWD_DEFER && sizeof(B) == 16;
+        constexpr bool DEFER = sizeof(B) == 16;
         typedef std::integral_constant<int, 8> NM8;
         typedef std::integral_constant<int, 4> NM4;
         // run all m-groups of segment S of layer L with epilogue epi(mb, acc)
@@ -321,7 +303,7 @@ __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
             SP_LAP(pipe.prof, 3);                                                            \
         })
 
-        // a masked layer: deferred (4-wave kernels) or group by group
+        // a masked layer: deferred (bf16 gradient operands) or group by group (fp32)
 #define SP_BWD_MASKED(L, DY, MK, OUT, PRE, STORE)                                               \
         do {                                                                                    \
             if constexpr (DEFER) bwd_layer_deferred<P, L, 0, POSE>(pipe, lane, DY, masked_units(MK, OUT), PRE, STORE); \

@@ -58,11 +58,9 @@ template <> struct Policy<PREC_FP32> {
 
 // bf16x3: operands are (head, tail) bf16 pairs, a product is three MFMAs (layout.h PREC_X3)
 struct bfpair { bf16x8 hi, lo; };
-#ifndef SP_X3_PREFETCH
-#define SP_X3_PREFETCH 4     // A-fragment pairs read ahead of their MFMAs (8 VGPRs each)
-#endif
 template <> struct Policy<PREC_X3> {
-    enum { PREC = PREC_X3, KJ = 8, CH = 8, FRAG_BYTES = 2048, LANE_BYTES = 16, G = group_g(PREC_X3), NWAVES = nwaves_of(PREC_X3), PREFETCH = SP_X3_PREFETCH };
+    // PREFETCH: A-fragment pairs read ahead of their MFMAs (8 VGPRs each)
+    enum { PREC = PREC_X3, KJ = 8, CH = 8, FRAG_BYTES = 2048, LANE_BYTES = 16, G = group_g(PREC_X3), NWAVES = nwaves_of(PREC_X3), PREFETCH = 4 };
     typedef bfpair B;
     typedef bfpair A;
     typedef __bf16 act_t;
@@ -96,17 +94,9 @@ template <> struct Policy<PREC_X3> {
 // row, mlp_bwd_impl.h bwd_layer_deferred) or W = 4 (one wave per SIMD with the whole register file, 128-row tiles, the forward
 // kernels' geometry).  Both are compiled into the library since round 6 (mlp_bwd_x3.hip / mlp_bwd_x3w4.hip) and api.hip picks one
 // per launch from the row count: a 512-ray step's coarse pass is 32 768 rows = 128 tiles of 256 rows -- half the chip idle for
-// a whole tile time -- but 256 tiles of 128 rows.  SP_X3_DGRAD_WAVES pins one geometry for every launch (A/B builds).
-#ifndef SP_X3_DGRAD_WAVES
-#define SP_X3_DGRAD_WAVES 0      // 0 = by row count (api.hip x3_dgrad_waves)
-#endif
+// a whole tile time -- but 256 tiles of 128 rows.  sparf_launch_kernel 3 / 4 pins one geometry at run time (A/B measurements).
 template <int W> struct PolicyX3DgradT {
-    enum { PREC = PREC_X3, KJ = 8, CH = 8, FRAG_BYTES = 2048, LANE_BYTES = 16, G = group_g(PREC_X3), NWAVES = W,
-#ifdef SP_X3_DGRAD_PREFETCH
-           PREFETCH = SP_X3_DGRAD_PREFETCH,
-#else
-           PREFETCH = (W == 8 ? 3 : 4),
-#endif
+    enum { PREC = PREC_X3, KJ = 8, CH = 8, FRAG_BYTES = 2048, LANE_BYTES = 16, G = group_g(PREC_X3), NWAVES = W, PREFETCH = (W == 8 ? 3 : 4),
            NPART = SP_X3_DGRAD_PARTS };
     typedef bf16x8 B;
     typedef bfpair A;
@@ -252,19 +242,13 @@ struct NoMid { template <class I, class N> SP_DEV void operator()(I, N) const {}
 // ~180 issue cycles wherever it sits, so this only pays where nothing else competes for the
 // CU's memory pipe: the inference kernels (bf16 0.74 -> 0.705 ms, bf16x3 2.06 -> 2.01 ms);
 // with activation stores in the same interval it is neutral to slightly negative.
-#ifndef SP_SPREAD_NUM
-#define SP_SPREAD_NUM 3      // the pieces are spread over the first NUM / DEN of the chunk's MFMAs
-#define SP_SPREAD_DEN 4
-#endif
+enum { SPREAD_NUM = 3, SPREAD_DEN = 4 };      // the pieces are spread over the first NUM / DEN of the chunk's MFMAs
 // Slot balance (bf16x3, NPART = 3): the MFMAs of a chunk run [k-step][part][m-block]; the LDS reads of the next fragments follow
 // the LAST part's MFMAs, so those gaps already hold two ds_read_b128 each.  A wave alone on its SIMD hides at most ~5 issue
 // slots behind one MFMA (MI355X_MICROARCH.md), so everything else is placed by kind: DMA pieces into last-part gaps (2 reads +
 // s_mov m0 + buffer_load = 4-5 slots), deferred-epilogue units (3-4 instructions each, mlp_fwd_impl.h) one per gap into the other
 // parts' gaps.  Placed by MFMA index alone (round 3a), a third of the units landed on the read gaps (6-10 slots) while a third
 // of the other gaps stayed empty.
-#ifndef SP_SLOT_BALANCE
-#define SP_SLOT_BALANCE 1
-#endif
 // index (inside a chunk of [k-step][part][m-block] MFMAs) of the t-th MFMA of the last part
 SP_DEV constexpr int last_part_slot(int t, int nmb, int npart) { return (t / nmb) * (npart * nmb) + (npart - 1) * nmb + t % nmb; }
 template <class Pipe, int NOFF, int NBYTES, int NMB = 1, int NPART = 1> struct SpreadFetch {
@@ -272,19 +256,12 @@ template <class Pipe, int NOFF, int NBYTES, int NMB = 1, int NPART = 1> struct S
     template <class I, class N> SP_DEV void operator()(I, N) const {
         if constexpr (Pipe::IS_SPREAD) {
             constexpr int i = I::value, n = N::value, NP = Pipe::PIECES;
-            if constexpr (SP_SLOT_BALANCE && NPART > 1) {
-                constexpr int nl = n / NPART, span = SP_SPREAD_NUM * nl / SP_SPREAD_DEN > 0 ? SP_SPREAD_NUM * nl / SP_SPREAD_DEN : 1;     // last-part MFMAs
-                static_for<NP>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value, t0 = j * span / NP, t = t0 < nl ? t0 : nl - 1;
-                    if constexpr (last_part_slot(t, NMB, NPART) == i) pipe.template fetch_piece<NOFF, NBYTES, j>(pipe.parity);
-                });
-            } else {
-                constexpr int span = SP_SPREAD_NUM * n / SP_SPREAD_DEN > 0 ? SP_SPREAD_NUM * n / SP_SPREAD_DEN : 1;
-                static_for<NP>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value, at0 = j * span / NP, at = at0 < n ? at0 : n - 1;
-                    if constexpr (at == i) pipe.template fetch_piece<NOFF, NBYTES, j>(pipe.parity);
-                });
-            }
+            // (NPART = 1: every MFMA is a last-part MFMA, last_part_slot(t) = t)
+            constexpr int nl = n / NPART, span = SPREAD_NUM * nl / SPREAD_DEN > 0 ? SPREAD_NUM * nl / SPREAD_DEN : 1;     // last-part MFMAs
+            static_for<NP>([&](auto jc) {
+                constexpr int j = decltype(jc)::value, t0 = j * span / NP, t = t0 < nl ? t0 : nl - 1;
+                if constexpr (last_part_slot(t, NMB, NPART) == i) pipe.template fetch_piece<NOFF, NBYTES, j>(pipe.parity);
+            });
         }
     }
 };
@@ -327,7 +304,7 @@ template <class P, class Pipe, class Epi, int NMB_PREV, int MB0_PREV, int BASE, 
     Pipe& pipe;
     Epi& epi;
     const f32x16 (&prev)[P::G];
-    static constexpr bool BALANCE = SP_SLOT_BALANCE && P::NPART > 1;
+    static constexpr bool BALANCE = P::NPART > 1;
     // eligible MFMA slots of the group before slot gi / in total
     static SP_DEV constexpr int eligible_before(int gi) {
         const int blk = P::NPART * NMB, el = (P::NPART - 1) * NMB, r = gi % blk;
@@ -408,29 +385,22 @@ SP_DEV int lane_voff(int n, int h) { return n * 16 + h * 512; }
 // Cache policy of the activation / gradient saves (buffer-instruction aux bits: 1 = sc0, 2 = nt,
 // 16 = sc1).  They are written once and read once, by a later kernel: non-temporal, so that 3.8 GB
 // of streaming stores per launch do not displace the 1-2 MB weight stream every CU re-reads from its
-// XCD's 4 MB L2.  Same-box A/B (tools/ab_kernels.sh, -DSP_SAVE_AUX=0 is the old default policy),
+// XCD's 4 MB L2.  Same-box A/B (tools/ab_kernels.sh) against aux 0, the old default policy,
 // bf16: training forward 1.25 -> 1.15 ms, dgrad 0.98 -> 0.88 ms, whole forward pass 1.21 -> 1.03 ms;
 // bf16x3: 2.58 -> 2.55, 1.44 -> 1.40 ms.
-#ifndef SP_SAVE_AUX
-#define SP_SAVE_AUX 2
-#endif
-// store k-step chunk C of vector v at byte offset BASE (+ C * 1024) of the tile block; PLANE1 = distance of the tail plane
-template <class P, int BASE, int C, int PLANE1> SP_DEV void bstore_chunk(__amdgpu_buffer_rsrc_t r, int voff, const typename P::B* v) {
+enum { SAVE_AUX = 2 };
+// store k-step chunk C of vector v at byte offset BASE (+ C * 1024) of the tile block (bf16x3 forward: the heads)
+template <class P, int BASE, int C> SP_DEV void bstore_chunk(__amdgpu_buffer_rsrc_t r, int voff, const typename P::B* v) {
     constexpr int OFF = BASE + C * 1024;
-#ifdef SP_PROBE_HALF_SAVES      // timing probe only (wrong results): every other 16-byte store dropped = the store count and bytes of 8-bit saves
-    if constexpr (C % 2 == 1) return;
-#endif
     if constexpr (sizeof(typename P::B) == 16) {            // one bf16x8 per k-step (bf16, bf16x3 dgrad)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[C]), r, voff, OFF, SP_SAVE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[C]), r, voff, OFF, SAVE_AUX);
     } else if constexpr (P::PREC == PREC_FP32) {
         u32x4 t;
         t[0] = __builtin_bit_cast(unsigned, v[4 * C]); t[1] = __builtin_bit_cast(unsigned, v[4 * C + 1]);
         t[2] = __builtin_bit_cast(unsigned, v[4 * C + 2]); t[3] = __builtin_bit_cast(unsigned, v[4 * C + 3]);
-        __builtin_amdgcn_raw_buffer_store_b128(t, r, voff, OFF, SP_SAVE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(t, r, voff, OFF, SAVE_AUX);
     } else {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[C].hi), r, voff, OFF, SP_SAVE_AUX);
-        if constexpr (nplanes_of(PREC_X3) == 2)
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[C].lo), r, voff, OFF + PLANE1, SP_SAVE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[C].hi), r, voff, OFF, SAVE_AUX);
     }
 }
 
@@ -497,13 +467,13 @@ SP_DEV u32x4 q8_pack16(bf16x8 a, bf16x8 b, float f) {
 // next block (measured: the first dword of a stored block replaced by the next block's first shifted operand, in the second
 // half of the workgroup's waves on some tiles).  Hence the explicit s_nop, pinned behind the store.
 template <int BASE, int C16, class BT> SP_DEV void q8_store16(__amdgpu_buffer_rsrc_t r, int voff, const BT* v, float f) {
-    __builtin_amdgcn_raw_buffer_store_b128(q8_pack16(hi_plane(v, 2 * C16), hi_plane(v, 2 * C16 + 1), f), r, voff, BASE + C16 * 1024, SP_SAVE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(q8_pack16(hi_plane(v, 2 * C16), hi_plane(v, 2 * C16 + 1), f), r, voff, BASE + C16 * 1024, SAVE_AUX);
     asm volatile("s_nop 1");
     __builtin_amdgcn_sched_barrier(0);
 }
 // the row's step, from both lane halves to the same address (no exec masking)
 template <int OFF> SP_DEV void q8_store_step(__amdgpu_buffer_rsrc_t r, int n, float amax) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, q8_step(amax)), r, n * 4, OFF, SP_SAVE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, q8_step(amax)), r, n * 4, OFF, SAVE_AUX);
 }
 
 // accumulator group initialised with the packed bias of m-blocks [mb0, mb0+NMB); the

@@ -45,9 +45,6 @@ static __device__ unsigned long long g_prof[10];
 // version: 24 % of the wave's time issuing VALU with the pipe idle): epi(mb, pair, stage, acc) runs stage
 // `stage` of elements 2*pair, 2*pair+1 of m-block mb; the units of a group arrive in order.
 enum { EPI_STAGES = 4 };
-#ifndef SP_LAZY_ACC_READ
-#define SP_LAZY_ACC_READ 1
-#endif
 // (DeferredEpi, the functor that places the units: mlp_dev.h)
 // MFMAs a group issues before chunk (s, kp) / in total
 template <class P, int L, int NMB> SP_DEV constexpr int group_mfmas_before(int s_end, int kp_end) {
@@ -125,7 +122,7 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
     constexpr int NB256 = 128 / KJ, NB128 = 64 / KJ, NBX0 = 32 / KJ, NBV = 16 / KJ;
     constexpr int AUX_FLOATS = xyz_exact(PREC) ? AUX_PK_FLOATS : BIAS_PK_FLOATS;
     // row routing (kernels.h) is compiled into the kernels of the precision far rows run in -- fp32 -- only: the bf16-operand
-    // kernels sit at their VGPR limit (tools/kernel_meta.sh) and are never launched routed (api.hip rejects other far precisions)
+    // kernels sit at their VGPR limit (tools/kernel_stream.py) and are never launched routed (api.hip rejects other far precisions)
     constexpr bool ROUTED = PREC == PREC_FP32;
 
     // LDS image: weight pipe | x0 stash | bias (+ xyz) table | c2f band weights | per-wave staging of the tile inputs
@@ -243,11 +240,7 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
             const float pv = first ? pvA : pvB;
             const float mk = c2f[k];
             float s, c;
-#ifdef SP_PROBE_NO_ENCODING     // timing probe (WRONG RESULTS): what the 15 sincosf per lane half cost the tile -- the upper bound of what a cross-tile
-            s = pv * mk; c = mk;    // software pipeline could hide of them (round 6; tools/evidence.sh fwdprobes6)
-#else
             sincosf(__fmul_rn(pv, ldexpf(3.14159274101257324219f, k)), &s, &c);
-#endif
             put_pair(i, __fmul_rn(s, mk), __fmul_rn(c, mk));
         }
         put_pair(15, h ? pz : px, h ? 0.0f : py);
@@ -309,7 +302,7 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
                     // instruction or statement right behind it (s_nop 0, 467 per tile; it does so behind an EMPTY statement too: the
                     // caution is about what the statement might hold -- a transcendental's result needs the wait state -- not about
                     // v_accvgpr_read_b32, whose result a dependent VALU instruction may read next like any other VALU result).
-                    constexpr bool LAZY = SP_LAZY_ACC_READ && sizeof...(deferred) > 0 && NW == 4;
+                    constexpr bool LAZY = sizeof...(deferred) > 0 && NW == 4;
                     if constexpr (LAZY && SAVE) {
                         asm volatile("v_accvgpr_read_b32 %0, %2\n\tv_max_i32 %0, 0, %0\n\tv_cmp_lt_i32 vcc, 0, %0\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc"
                                      : "=v"(yi), "+v"(mask_bits) : "a"(x) : "vcc");     // (volatile: stays in its unit; the 4-wave kernels' accumulators live in AGPRs)
@@ -324,7 +317,7 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
                     (st == 0 ? e_v0 : e_v1) = __builtin_bit_cast(float, yi);
                 } else if constexpr (st == 2) {
                     // (the pack stays behind its slot's MFMA: moved up in front of it, next to stage 1's statement, it is padded too)
-                    if constexpr (SP_LAZY_ACC_READ && sizeof...(deferred) > 0 && NW == 4) __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (sizeof...(deferred) > 0 && NW == 4) __builtin_amdgcn_sched_barrier(0);
                     if constexpr (PREC == PREC_FP32) {
                         out[q0] = e_v0;
                         out[q0 + 1] = e_v1;
@@ -357,7 +350,7 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
                         mask_w[mb / 2] = mask_bits;                   // 32 pushes since the last hand-over: the word is complete
 #ifndef SP_PROBE_NO_STORES
                         if constexpr (mb == NMBL - 1)
-                            __builtin_amdgcn_raw_buffer_store_b128(mask_w, srs, lane * 16, save_mask_tile_off(AF, decltype(sbc)::value), SP_SAVE_AUX);
+                            __builtin_amdgcn_raw_buffer_store_b128(mask_w, srs, lane * 16, save_mask_tile_off(AF, decltype(sbc)::value), SAVE_AUX);
 #endif
                     }
                 }
@@ -393,7 +386,7 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
                     constexpr int c0 = g * NST / ng, c1 = (g + 1) * NST / ng;
                     constexpr int BASE = save_buf_tile_off(AF, sb) + (col0 / CH) * 512;
                     if constexpr (SAVE && c1 > c0)
-                        static_for<c1 - c0>([&](auto cc) { bstore_chunk<P, BASE, c0 + decltype(cc)::value, (int)save_plane_tile_bytes(AF)>(srs, lvo, v); });
+                        static_for<c1 - c0>([&](auto cc) { bstore_chunk<P, BASE, c0 + decltype(cc)::value>(srs, lvo, v); });
                 }
             };
         };
@@ -406,12 +399,9 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
 #define SP_SB(b) std::integral_constant<int, b>{}
         // deferred epilogue (fwd_layer) in every kernel.  Rounds 2-4 left the 8-wave bf16 kernels out ("no registers for a second accumulator
         // set, and a partner wave to cover the epilogue") without compiling them: they need 254-256 registers either way and spill LESS with it
-        // (5 instead of 8, tools/kernel_meta.sh); bit-identical, training forward 1.061-1.065 -> 1.030-1.045 ms, with 8-bit saves 1.035-1.042 ->
+        // (5 instead of 8, tools/kernel_stream.py); bit-identical, training forward 1.061-1.065 -> 1.030-1.045 ms, with 8-bit saves 1.035-1.042 ->
         // 1.005-1.011, inference 0.663 -> 0.654-0.660 (round 5, profiles/r05_kernel_ab_fwd_defer_bf16.log; the data-gradient kernels: mlp_bwd_impl.h)
-#ifndef SP_DEFER_EPI
-#define SP_DEFER_EPI 1
-#endif
-        constexpr bool DEFER = SP_DEFER_EPI;
+        constexpr bool DEFER = true;        // (layer 9 below: three outputs, nothing to defer)
 
         // (the mask of layer l's OUTPUT lives next to the saved buffer that holds it as the next layer's input)
         { auto e = relu_to(hA, MB8{}, SP_SB(SB_H0)); fwd_layer<P, 0, DEFER, Pipe>(pipe, bias_pk, lane, bx0, bx0, e, saver(SP_SB(SB_XS), C256{}, NST_X0{}, bx0, qf_a), pt); }
@@ -461,16 +451,12 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
         }
 #undef SP_SB
         SP_LAP(pipe.prof, 9);
-#ifdef SP_PROBE_NO_TILE_END     // timing probe (WRONG RESULTS): the tile's last phase -- sigmoid + colour stores -- reduced to one store (keeps z0..z2 live)
-        if (valid && h == 0 && z0 + z1 + z2 == 12345.678f) a.rgb[row * 3] = z0;
-#else
         if (valid && h == 0) {
             float* o = a.rgb + (ROUTED ? routed_row(row, a.nsamp, a.row_stride, a.row_off) : row) * 3;
             o[0] = 1.0f / (1.0f + expf(-z0));
             o[1] = 1.0f / (1.0f + expf(-z1));
             o[2] = 1.0f / (1.0f + expf(-z2));
         }
-#endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     pipe.drain();      // the last prefetches land before the workgroup gives up its LDS

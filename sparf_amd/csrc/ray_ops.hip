@@ -492,7 +492,7 @@ __global__ void __launch_bounds__(256) far_transplant_kernel(const char* __restr
 
 int launch_far_transplant(int main_prec, const void* far_area, void* main_area, int64_t frows, int far_count, int nsamp, hipStream_t s) {
     if (frows <= 0) return 0;
-    if (main_prec == PREC_FP32 || nplanes_of(main_prec) != 1) return 1;       // bf16-plane save areas only (bf16, bf16x3 with head planes)
+    if (main_prec == PREC_FP32) return 1;       // bf16-plane save areas only (bf16, bf16x3: its head planes)
     const int64_t ntiles = (frows + 31) / 32;
     hipLaunchKernelGGL(far_transplant_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, (const char*)far_area, (char*)main_area, frows, far_count, nsamp,
                        save_tile_bytes(main_prec), save_mask_tile_off(main_prec, 0));

@@ -20,7 +20,7 @@ flips the units whose pre-activation is within e of zero, and a gradient sum ove
 incoherent signs (this test's random loss functional is the worst case) sees that as a relative
 error that does not average out.  Measured worst tensor (always mlp_feat.0.weight, shrinking towards
 the output layers): fp32 reference 1.0e-3 .. 1.5e-3, HIP fp32 0.8e-3 .. 1.7e-3, bf16x3 6e-3 .. 8e-3 --
-and 5.2e-3 with the full-precision backward (-DSP_X3_SAVE_PLANES=2 -DSP_X3_DGRAD_FULL: rgb-layer
+and 5.2e-3 with the full-precision backward (-DSP_X3_SAVE_PLANES=2 -DSP_X3_DGRAD_FULL, code retired, last in ebe6c54: rgb-layer
 gradient 6e-6, feature layers unchanged), i.e. the bf16-rounded backward operands of the default
 build add ~30 % to a floor set by the forward's 2e-5; DESIGN.md section 2 has the table.
 Run with `pytest -m gpu`."""

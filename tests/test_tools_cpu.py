@@ -33,6 +33,28 @@ kernel:
     assert m.gaps_of(asm) == [2, 0]          # instructions before the first and after the last MFMA do not count
 
 
+def test_kernel_stream_diff_compares_listings_without_addresses_and_comments():
+    m = _load("tools/kernel_stream.py", "kernel_stream_diff")
+    head = ["\ts_load_dword s0, s[0:1], 0x0                                // 000000001000:", "\ts_waitcnt lgkmcnt(0)   // 000000001008:"]
+    loop = ["\tv_mfma_f32_32x32x16_bf16 a[0:15], v[0:3], v[4:7], a[0:15]   // 000000001010:", "\tds_read_b128 v[0:3], v8   // 000000001018:",
+            "\tv_mfma_f32_32x32x16_bf16 a[0:15], v[0:3], v[4:7], a[0:15]   // 000000001020:", "\ts_cbranch_scc1 65529   // 000000001028: <k+0x10>"]
+    tail = ["\ts_endpgm   // 00000000102C:", ""]
+    a = {"k_same": head + loop + tail, "k_prologue": head + loop + tail, "k_loop": head + loop + tail, "k_gone": head + tail}
+    moved = [line.replace("0000000010", "0000000320") for line in head + loop + tail]           # the same code at another address
+    shifted = [line.replace("0000000010", "0000000011") for line in head[1:] + loop + tail]
+    b = {"k_same": moved,
+         "k_prologue": [head[0], "\ts_mov_b32 s1, 0   // 000000001004:"] + shifted,                # one instruction more, before the loop
+         "k_loop": head + [loop[0], loop[1].replace("b128 v[0:3]", "b64 v[0:1]")] + loop[2:] + tail,    # one instruction changed between the MFMAs
+         "k_new": head + tail}
+    assert m.mfma_loops(m.parsed(a["k_loop"])) == [(0x1010, 0x1028)]
+    got = {name: (verdict, d) for name, verdict, d in m.compare_listings(a, b)}
+    assert {k: v[0] for k, v in got.items()} == {"k_same": "IDENTICAL", "k_prologue": "DIFFER", "k_loop": "DIFFER", "k_gone": "ONLY_A", "k_new": "ONLY_B"}
+    d = got["k_prologue"][1]
+    assert d["lines"] == (7, 8) and d["hist"] == {"s_mov_b32": [0, 1]} and d["only"] == (0, 1) and d["in_tile_loop"] == (0, 0)
+    d = got["k_loop"][1]
+    assert d["lines"] == (7, 7) and d["hist"] == {"ds_read_b128": [1, 0], "ds_read_b64": [0, 1]} and d["only"] == (1, 1) and d["in_tile_loop"] == (1, 1)
+
+
 def test_fp8_emulation_matches_torch_casts():
     """tests/tools/save_precision_study.py rounds with its own arithmetic (a per-tile scale, then the 8-bit grid): with the scale
     forced to one the grid must be torch's float8_e4m3fn / float8_e5m2 (round to nearest even, subnormals, saturation)."""
@@ -66,19 +88,34 @@ def test_emulated_linear_is_the_plain_one_without_rounding():
 
 
 def test_shipped_kernels_have_no_experiment_or_probe_flag_on():
-    """The kernel sources carry measured experiments as build flags: the defaults are the shipped configuration,
-    the probes give WRONG RESULTS by design and must never be defined in the sources or by sparf_amd.build."""
+    """The kernel sources hold the shipped configuration and the instruments still in use.  The switches of settled
+    experiments are retired: their names appear in no code file (the documents keep the record).  The switches that stay have the
+    shipped value as their guarded default; the probes give WRONG RESULTS by design and must never be defined in the sources or by
+    sparf_amd.build."""
     import re
     from sparf_amd import build as B
     src = {f: open(os.path.join(B.CSRC, f)).read() for f in os.listdir(B.CSRC) if f.endswith((".h", ".hip", ".cpp"))}
     text = "\n".join(src.values())
-    expected = {"SP_BWD_DEFER": "1", "SP_DEFER_EPI": "1", "SP_BWD_SPREAD": "1", "SP_BWD_STAGGER": "0", "SP_X3_DGRAD_WAVES": "0", "SP_X3_DGRAD_PARTS": "2",
-                "SP_WG_SPREAD": "0", "SP_WG_Q8_HALVES": "0", "SP_SAVE_AUX": "2", "SP_XYZ_EXACT": "0", "SP_LAZY_ACC_READ": "1", "SP_SLOT_BALANCE": "1"}
+    retired = ("SP_WG_Q8_HALVES", "SP_WG_SPREAD", "SP_WG_NBUF_MAX", "SP_WG_NT", "SP_WG_X3_ROWS", "SP_BWD_STAGGER", "SP_BWD_DEFER", "SP_BWD_SPREAD",
+               "SP_DEFER_EPI", "SP_LAZY_ACC_READ", "SP_SLOT_BALANCE", "SP_SPREAD_NUM", "SP_SPREAD_DEN", "SP_X3_PREFETCH", "SP_X3_DGRAD_PREFETCH",
+               "SP_SAVE_AUX", "SP_X3_DGRAD_WAVES", "SP_X3_DGRAD_FULL", "SP_X3_SAVE_PLANES", "SP_PROBE_NO_ENCODING", "SP_PROBE_NO_TILE_END",
+               "SP_PROBE_HALF_SAVES", "wgrad_q8h_kernel", "launch_wgrad_partials", "launch_wgrad_reduce", "nplanes_of")
+    code = dict(src)
+    code["build.py"] = open(os.path.join(B.HERE, "build.py")).read()
+    tools = os.path.join(ROOT, "tools")
+    for d, _, files in os.walk(tools):
+        for f in files:
+            if not f.endswith((".md", ".rst", ".txt")):
+                code[os.path.relpath(os.path.join(d, f), ROOT)] = open(os.path.join(d, f), errors="replace").read()
+    for name in retired:
+        hits = [f for f, t in code.items() if name in t]
+        assert not hits, f"{name} is retired but still named in {hits}"
+    expected = {"SP_X3_DGRAD_PARTS": "2", "SP_XYZ_EXACT": "0"}
     for name, val in expected.items():
         m = re.search(r"#ifndef %s\s*\n#define %s (\S+)" % (name, name), text)
         assert m, f"{name}: no guarded default found"
         assert m.group(1) == val, (name, m.group(1), "shipped default is", val)
-    for name in ("SP_PROBE_NO_STORES", "SP_PROBE_NO_DMA", "SP_PROBE_NO_BARRIER", "SP_PROBE_HALF_SAVES", "SP_PROBE_NO_ENCODING", "SP_PROBE_NO_TILE_END", "SP_PROF",
-                 "SP_X3_DGRAD_FULL"):
+    for name in ("SP_PROBE_NO_STORES", "SP_PROBE_NO_DMA", "SP_PROBE_NO_BARRIER", "SP_PROF"):
+        assert name in text, f"{name}: the instrument is gone from the sources"
         assert not re.search(r"^\s*#\s*define\s+%s\b" % name, text, flags=re.M), f"{name} is defined in the sources"
         assert not any(name in f for f in B.FLAGS), f"{name} is passed by the default build"

@@ -2,7 +2,7 @@
 (tools/ab_kernels.sh, tools/evidence.sh ab / dgradprobes):
 
     python tools/build_flag_variant.py <tag> "<flags>" <translation units the flags affect, comma-separated>
-    python tools/build_flag_variant.py nodefer "-DSP_BWD_DEFER=0" mlp_bwd.hip,mlp_bwd_q8.hip
+    python tools/build_flag_variant.py parts1 "-DSP_X3_DGRAD_PARTS=1" mlp_bwd_x3.hip,mlp_bwd_x3w4.hip,mlp_bwd_q8.hip
     python tools/build_flag_variant.py p0 "-DSP_PROF" mlp_bwd.hip            # wave-time accounting of the data-gradient kernel
 
 -> sparf_amd/libsparf_hip_<tag>.so (objects in sparf_amd/csrc/build_<tag>/; the other units are linked from the default build).

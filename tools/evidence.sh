@@ -25,8 +25,6 @@
 #   geometry     bf16x3 data-gradient kernel, 8-wave vs 4-wave geometry by row count (api.hip x3_dgrad_waves) -> r06_dgrad_geometry.log
 #   smallstep    rocprofv3 kernel stats of a 512-ray step replayed as one hipGraph                    -> r06_r512_kernel_stats.csv
 #   registration joint pose-NeRF registration, oracle and HIP side by side (tests/tools/registration_run.py) -> r06_registration.json
-#   fwdprobes6   the bf16x3 training forward without its encoding / tile end (upper bound of a cross-tile pipeline) -> r06_fwd_pipeline_probes.log
-#   q8halves     8-bit weight-gradient jobs as half jobs, two resident workgroups per CU (variant library)  -> r06_wgrad_q8_halves.log
 #   dgradprobes  wave-time accounting ("lap table") of the data-gradient kernel + its timing probes (variant libraries of tools/build_flag_variant.py) -> r06_dgrad_lap_table.log
 #
 # live / seeds: the reference tree is NOT part of the repository snapshot.  A builder who wants these sections packs it first, in the
@@ -104,9 +102,9 @@ PY
       AB_PRECS="${AB_PRECS:-bf16x3 bf16x3+q8}" bash tools/ab_kernels.sh ${AB_TAGS:-} 2>&1 | tee gpurun_out/${TAG}_kernel_ab_${AB_NAME:-variants}.log ;;
     dgradprobes)   # wave-time accounting of the data-gradient kernel (mlp_dev.h Prof) and its timing probes; build the libraries first:
       #   for v in "p0:-DSP_PROF" "p1:-DSP_PROF -DSP_PROBE_NO_STORES" "p2:-DSP_PROF -DSP_PROBE_NO_DMA" "p3:-DSP_PROF -DSP_PROBE_NO_DMA -DSP_PROBE_NO_STORES" \
-      #            "p4:-DSP_PROF -DSP_PROBE_NO_DMA -DSP_PROBE_NO_STORES -DSP_PROBE_NO_BARRIER" "nodeferp:-DSP_PROF -DSP_BWD_DEFER=0"; do
+      #            "p4:-DSP_PROF -DSP_PROBE_NO_DMA -DSP_PROBE_NO_STORES -DSP_PROBE_NO_BARRIER"; do
       #     python tools/build_flag_variant.py ${v%%:*} "${v#*:}" mlp_bwd.hip; done
-      for tag in ${PROBE_TAGS:-nodeferp p0 p1 p2 p3 p4}; do
+      for tag in ${PROBE_TAGS:-p0 p1 p2 p3 p4}; do
         [ -f sparf_amd/libsparf_hip_$tag.so ] || continue
         for P in ${PROBE_PRECS:-bf16x3 bf16}; do
           echo "== lib $tag prec $P"
@@ -119,27 +117,8 @@ PY
         echo "== lib $tag prec bf16x3"
         SPARF_LIB=$PWD/sparf_amd/libsparf_hip_$tag.so timeout 300 python tools/kernel_bench.py bf16x3 2>&1 | grep -A1 "^fwd save"
       done | tee gpurun_out/${TAG}_fwd_lap_table.log ;;
-    fwdprobes6)   # round 6: what a cross-tile software pipeline of the bf16x3 training forward could hide at most -- the kernel without its
-      # encoding (15 sincosf per lane half) and / or without its tile end (sigmoid + colour stores); WRONG RESULTS, timing only.  Libraries:
-      #   for v in "e0:-DSP_PROBE_NO_ENCODING" "e1:-DSP_PROBE_NO_TILE_END" "e2:-DSP_PROBE_NO_ENCODING -DSP_PROBE_NO_TILE_END"; do
-      #     python tools/build_flag_variant.py ${v%%:*} "${v#*:}" mlp_fwd_x3_train.hip; done
-      for rep in 1 2 3; do for tag in default e0 e1 e2; do
-        if [ "$tag" = default ]; then unset SPARF_LIB; else [ -f sparf_amd/libsparf_hip_$tag.so ] || continue; export SPARF_LIB=$PWD/sparf_amd/libsparf_hip_$tag.so; fi
-        echo "== rep $rep lib $tag: $(KB_ONLY='fwd save' timeout 300 python tools/kernel_bench.py bf16x3 2>&1 | grep '^fwd save')"
-      done; done | tee gpurun_out/${TAG}_fwd_pipeline_probes.log
-      unset SPARF_LIB ;;
     registration) # joint pose-NeRF registration, oracle (torch ops) and HIP renderer side by side (tests/tools/registration_run.py)
       timeout ${REG_TIMEOUT:-2400} python tests/tools/registration_run.py --steps ${REG_STEPS:-3000} --seeds ${REG_SEEDS:-3} ${REG_ARGS:-} --out gpurun_out/${TAG}_registration.json 2>&1 | grep -v "Warning\|warnings.warn" | tail -60 ;;
-    q8halves)     # round 6 experiment: the 8-bit weight-gradient jobs as half jobs, two resident workgroups per CU (wgrad.hip SP_WG_Q8_HALVES).
-      # Library:  python tools/build_flag_variant.py q8h "-DSP_WG_Q8_HALVES=1" wgrad.hip     (profiles/r06_wgrad_q8_halves.log was taken with a
-      # run-time switch between the same two kernel sets, before the switch became this build flag)
-      [ -f sparf_amd/libsparf_hip_q8h.so ] || { echo "no sparf_amd/libsparf_hip_q8h.so: section skipped"; continue; }
-      SPARF_LIB=$PWD/sparf_amd/libsparf_hip_q8h.so timeout 600 python -m pytest tests/test_q8_saves_gpu.py -m gpu -q -p no:cacheprovider 2>&1 | grep -v "Warning\|warnings.warn\|^$" | tail -4
-      for rep in 1 2 3; do for h in 0 1; do for P in bf16x3+q8 bf16+q8; do
-        if [ $h = 1 ]; then export SPARF_LIB=$PWD/sparf_amd/libsparf_hip_q8h.so; else unset SPARF_LIB; fi
-        echo "== rep $rep halves $h prec $P: $(KB_ONLY=wgrad,pass timeout 300 python tools/kernel_bench.py $P 2>&1 | grep -E '^(wgrad|pass bwd)' | tr '\n' ' ')"
-      done; done; done | tee gpurun_out/${TAG}_wgrad_q8_halves.log
-      unset SPARF_LIB ;;
     lazyab)       # configs 3 / 4 with and without lazy batching of the back-to-back correspondence renders, same box, alternating
       for rep in 1 2 3; do for lz in 1 0; do for c in 3 4; do
         echo "== rep $rep config $c lazy $lz: $(SPARF_LAZY_BATCH=$lz timeout 400 python bench.py --config $c --steps 20 $quick --no-roofline --no-telemetry | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(round(d["value"]), "rays/s", round(d["ms_per_step"],2), "ms; sustained", round(d["sustained"]["value"]))')"

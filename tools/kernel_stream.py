@@ -2,6 +2,9 @@
 
     python tools/kernel_stream.py [translation unit ...]        (default: the two config-1 units of the bf16x3 mode; `all` = every
                                                                  unit built from mlp_fwd_impl.h / mlp_bwd_impl.h)
+    python tools/kernel_stream.py diff <object dir A> <object dir B>     (every kernel of every unit both directories hold: IDENTICAL, or
+                                                                 DIFFER with what differs; e.g. sparf_amd/csrc_<tag> of tools/build_variant.py
+                                                                 against sparf_amd/csrc/build -- a refactor's proof of "same machine code")
 
 Reads the gfx950 code object out of sparf_amd/csrc/build/<unit>.o (compiles the unit into a scratch directory when there is no
 object newer than its sources) and prints, per kernel: MFMAs, all other instructions, s_nop, v_readlane_b32 / v_writelane_b32
@@ -75,8 +78,8 @@ def count_stream(lines):
             "v_writelane_b32": c["v_writelane_b32"], "v_pk_add_f32": c["v_pk_add_f32"]}
 
 
-def streams_of(co):
-    """{kernel name: counts} from the disassembly of the code object"""
+def listings_of(co):
+    """{kernel name: disassembly lines} of the code object"""
     txt = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], text=True)
     out, cur = {}, None
     for line in txt.split("\n"):
@@ -85,7 +88,73 @@ def streams_of(co):
             cur = out.setdefault(m.group(1), [])
         elif cur is not None:
             cur.append(line)
-    return {k: count_stream(v) for k, v in out.items()}
+    return out
+
+
+def streams_of(co):
+    """{kernel name: counts} from the disassembly of the code object"""
+    return {k: count_stream(v) for k, v in listings_of(co).items()}
+
+
+def canonical(lines):
+    """a listing as comparable text: leading addresses and `//` comments (addresses, encodings) dropped, empty lines too"""
+    return [t for t, _ in parsed(lines)]
+
+
+def parsed(lines):
+    """[(canonical text, address or None)] of a listing (the address: what llvm-objdump prints behind `//`)"""
+    out = []
+    for line in lines:
+        code, _, comment = line.partition("//")
+        t = " ".join(re.sub(r"^\s*[0-9a-f]+:?\s+(?=\S)", "", code).split())
+        if t and t != "...":                                  # ("...": zero padding)
+            m = re.match(r"\s*([0-9A-Fa-f]+):", comment)
+            out.append((t, int(m.group(1), 16) if m else None))
+    return out
+
+
+def mfma_loops(listing):
+    """address ranges [target, branch] of the backward branches that enclose an MFMA: the tile loops"""
+    mf = [a for t, a in listing if t.startswith("v_mfma") and a is not None]
+    out = []
+    for t, a in listing:
+        if t.startswith(("s_branch", "s_cbranch")) and a is not None and t.split()[-1].isdigit():
+            imm = int(t.split()[-1])
+            target = a + 4 + 4 * (imm - 65536 if imm >= 32768 else imm)
+            if target <= a and any(target <= m <= a for m in mf):
+                out.append((target, a))
+    return out
+
+
+def compare_listings(a, b):
+    """[(kernel name, verdict, detail)] over two {kernel name: disassembly lines}: verdict IDENTICAL | DIFFER | ONLY_A | ONLY_B.
+    IDENTICAL = the same text once addresses and comments are dropped.  detail of DIFFER: line counts of both sides and, with the
+    branch distances masked (they move with every instruction in between), the lines only one side has: how many, how many
+    of them inside a loop that holds MFMAs (a tile loop), and their mnemonics ({mnemonic: [in A only, in B only]})."""
+    import difflib
+    out = []
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            out.append((name, "ONLY_A" if name in a else "ONLY_B", None))
+            continue
+        pa, pb = parsed(a[name]), parsed(b[name])
+        if [t for t, _ in pa] == [t for t, _ in pb]:
+            out.append((name, "IDENTICAL", {"lines": (len(pa), len(pb))}))
+            continue
+        mask = lambda t: re.sub(r"^(s_c?branch\S*) \d+$", r"\1 .", t)
+        la, lb = [mask(t) for t, _ in pa], [mask(t) for t, _ in pb]
+        loops = (mfma_loops(pa), mfma_loops(pb))
+        hist, only, in_loop = {}, [0, 0], [0, 0]
+        for tag, i0, i1, j0, j1 in difflib.SequenceMatcher(None, la, lb, autojunk=False).get_opcodes():
+            if tag == "equal":
+                continue
+            for side, (lines, addrs, x0, x1) in enumerate(((la, pa, i0, i1), (lb, pb, j0, j1))):
+                for x in range(x0, x1):
+                    hist.setdefault(lines[x].split()[0], [0, 0])[side] += 1
+                    only[side] += 1
+                    in_loop[side] += any(addrs[x][1] is not None and lo <= addrs[x][1] <= hi for lo, hi in loops[side])
+        out.append((name, "DIFFER", {"lines": (len(pa), len(pb)), "hist": hist, "only": tuple(only), "in_tile_loop": tuple(in_loop)}))
+    return out
 
 
 # every translation unit built from mlp_dev.h + mlp_fwd_impl.h / mlp_bwd_impl.h
@@ -100,7 +169,65 @@ def figures(unit):
     return {k: dict(streams.get(k, {}), **v) for k, v in notes.items()}
 
 
+def kernel_names(mangled):
+    """{mangled: demangled name without return type and argument list}: `sparf::wgrad_kernel<0, false>` stays the same kernel
+    when its argument list changes"""
+    mangled = list(mangled)
+    if not mangled:
+        return {}
+    import shutil
+    filt = shutil.which("llvm-cxxfilt", path=LLVM) or shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+    if not filt:
+        return {m: m for m in mangled}                       # (no demangler: a changed argument list then shows as two kernels)
+    dem = subprocess.check_output([filt] + mangled, text=True).split("\n")
+    out = {}
+    for m, d in zip(mangled, dem):
+        if d.endswith(")"):
+            depth, i = 0, len(d)
+            while i > 0:
+                i -= 1
+                depth += d[i] == ")"
+                depth -= d[i] == "("
+                if depth == 0:
+                    break
+            d = d[:i]
+        out[m] = d[5:] if d.startswith("void ") else d
+    return out
+
+
+def diff_dirs(dir_a, dir_b):
+    """print the comparison of every unit (object file name) the two object directories share"""
+    units = lambda d: {f for f in os.listdir(d) if f.endswith(".o")}
+    ua, ub = units(dir_a), units(dir_b)
+    for f in sorted(ua ^ ub):
+        print(f"{f}: only in {dir_a if f in ua else dir_b}")
+    with tempfile.TemporaryDirectory() as da, tempfile.TemporaryDirectory() as db:
+        for f in sorted(ua & ub):
+            try:
+                ca, cb = code_object(os.path.join(dir_a, f), da), code_object(os.path.join(dir_b, f), db)
+            except subprocess.CalledProcessError:
+                print(f"{f}: no gfx950 code object (host-only unit)")
+                continue
+            # (kernels only -- the names the notes list; not device functions or labels)
+            by_name = lambda d, names: {names[k]: v for k, v in d.items() if k in names}
+            ka, kb = kernel_names(notes_of(ca)), kernel_names(notes_of(cb))
+            na, nb = by_name(notes_of(ca), ka), by_name(notes_of(cb), kb)
+            sa, sb = by_name(streams_of(ca), ka), by_name(streams_of(cb), kb)
+            for name, verdict, d in compare_listings(by_name(listings_of(ca), ka), by_name(listings_of(cb), kb)):
+                if verdict != "DIFFER":
+                    print(f"{f}: {name}: {verdict}" + (f" ({d['lines'][0]} lines)" if d else ""))
+                    continue
+                print(f"{f}: {name}: DIFFER  lines {d['lines'][0]} -> {d['lines'][1]}  mfma {sa[name]['mfma']} -> {sb[name]['mfma']}")
+                print(f"    lines only in A / B: {d['only'][0]} / {d['only'][1]}, of them inside a loop with MFMAs (tile loop): {d['in_tile_loop'][0]} / {d['in_tile_loop'][1]}")
+                net = {k: v for k, v in sorted(d["hist"].items()) if v[0] != v[1]}
+                print("    mnemonics whose counts differ (A/B): " + ("  ".join(f"{k} {v[0]}/{v[1]}" for k, v in net.items()) or "none: operands only"))
+                print("    notes: " + "  ".join(f"{k} {na[name][k]} -> {nb[name][k]}" + ("" if na[name][k] == nb[name][k] else " (!)") for k in NOTE_KEYS))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["diff"]:
+        diff_dirs(sys.argv[2], sys.argv[3])
+        sys.exit(0)
     for unit in MLP_UNITS if sys.argv[1:] == ["all"] else sys.argv[1:] or ["mlp_fwd_x3_train.hip", "mlp_bwd_x3.hip"]:
         for name, f in figures(unit).items():
             print(f"{unit}: {name}")
