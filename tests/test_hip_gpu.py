@@ -337,11 +337,12 @@ def test_large_pass_beyond_the_old_2GiB_limit():
 @pytest.mark.parametrize("R,N", [(70, 24), (1024, 32), (515, 64), (1536, 64)])
 def test_both_geometries_of_the_bf16x3_data_gradient_kernel_are_bit_identical(R, N, pose):
     """The bf16x3 dgrad ships as an 8-wave / 256-row and a 4-wave / 128-row kernel and sparf_pass_backward picks one per launch from the
-    row count (api.hip x3_dgrad_waves, round 6).  Pinned through sparf_launch_kernel (3 / 4), both must leave the SAME bytes in the
+    row count (pass_plan.h x3_dgrad_rows8, round 6).  Pinned through sparf_launch_kernel (3 / 4), both must leave the SAME bytes in the
     workspace -- gradient area (every dY the weight-gradient kernel reads), d point and d view encoding -- on ragged row counts too
     (1 680 rows: neither a multiple of 128 nor of 256; 32 960: a partial last round of either tile size), and so must the launch plan
     the pass itself uses (which = 1): at 98 304 rows on a 256-CU chip that is one full round of 256-row tiles in 8 waves followed by the
-    remaining 32 768 rows in 4 waves (api.hip x3_dgrad_rows8)."""
+    remaining 32 768 rows in 4 waves.  The SAME bytes are the ones sparf_pass_backward itself left: each relaunch is compared with a
+    snapshot of the workspace taken right behind the pass call, which ties the single-kernel launches to what the pass launched."""
     import ctypes
     lib = L.load()
     d = dev()
@@ -362,11 +363,81 @@ def test_both_geometries_of_the_bf16x3_data_gradient_kernel_are_bit_identical(R,
     ba, gp, dc, dd, keep2 = ops.build_pass_bwd(prec, c, dr, t, None, 0.0, False, packed, c2f, save, out, grads, pose)
     L.check(lib.sparf_pass_backward(ctypes.byref(ba), s), "bwd")            # fills d sigma / d z of the workspace
     ws = keep2[0]
+    torch.cuda.synchronize()
+    of_the_pass = ws.clone()
     images = []
     for which in (3, 4, 1):
         L.check(lib.sparf_launch_kernel(which, ctypes.byref(fa), ctypes.byref(ba), s), "dgrad")
         torch.cuda.synchronize()
         images.append(ws.clone())
+        assert torch.equal(images[-1], of_the_pass), (which, int((images[-1] != of_the_pass).sum()))
     assert torch.equal(images[0], images[1]), int((images[0] != images[1]).sum())
     assert torch.equal(images[0], images[2]), int((images[0] != images[2]).sum())
     assert int((images[0] != 0).sum()) > ws.numel() // 8                     # (the comparison is of real content)
+
+
+@pytest.mark.parametrize("pose", [False, True], ids=["fixed_pose", "pose_grad"])
+@pytest.mark.parametrize("R,N", [(70, 24), (333, 64)])
+@pytest.mark.parametrize("prec_name", ["fp32", "bf16", "bf16x3", "bf16x3+q8"])
+def test_single_kernel_launches_leave_the_bytes_of_the_pass(prec_name, R, N, pose):
+    """sparf_launch_kernel promises "the arguments the pass-level calls would give it" (sparf_hip.h).  Held to it byte for byte: what
+    sparf_pass_forward left in sigma_raw, rgb_samples and the save area is overwritten and must come back from which = 0; what
+    sparf_pass_backward left in the workspace and in grad_params is overwritten -- the gradient area, the split-K partial blocks and,
+    with pose gradients, d point / d view encoding; d sigma / d z / d |ray| are the relaunches' inputs and stay -- and must come back
+    from which = 1 then 2.  The areas hold the overwriting byte before the pass calls too, so that padding bytes no kernel writes
+    compare equal and every byte a pass call wrote has to be written again.  1 680 rows are ragged against the 128- and 256-row
+    workgroup tiles.  No far rows: which = 0 is the main launch only."""
+    import ctypes
+    lib = L.load()
+    d = dev()
+    prec = L.PREC_IDS[prec_name]
+    FILL = 0x55
+
+    def same(x, want):
+        return torch.equal(x.view(torch.uint8), want.view(torch.uint8))
+
+    def written(x):                                       # bytes of a snapshot that a pass call wrote
+        return int((x.view(torch.uint8) != FILL).sum())
+
+    opt = small_opt(barf_c2f=[0.4, 0.7])
+    sd = make_state_dict(opt, 21, progress=0.55)
+    center, dirs, jitter, _ = make_scene(R, N, 6)
+    t = O.sample_depth(opt, 1, R, N, [1.2, 5.2], "train", jitter)[0, :, :, 0].to(d).contiguous()
+    plist = params_list(sd, d)
+    packed = ops.pack_weights(plist, prec)
+    c2f = ops.c2f_weights(sd["progress"].to(d), opt.barf_c2f, d)
+    c, dr = center.to(d).contiguous(), dirs.to(d).contiguous()
+    s = L.stream_ptr(d)
+    fa, out, save, keep1 = ops.build_pass_fwd(prec, c, dr, t, None, 0.0, False, packed, c2f, True)
+    fwd_bufs = dict(sigma_raw=out["sigma_raw"], rgb_samples=out["rgb_samples"], save=save)
+    save.fill_(FILL)
+    L.check(lib.sparf_pass_forward(ctypes.byref(fa), s), "fwd")
+    torch.cuda.synchronize()
+    of_the_pass = {k: x.clone() for k, x in fwd_bufs.items()}
+    assert all(written(x) > x.numel() * x.element_size() // 8 for x in of_the_pass.values())       # (the comparison is of real content)
+    for x in fwd_bufs.values():
+        x.view(torch.uint8).fill_(FILL)
+    L.check(lib.sparf_launch_kernel(0, ctypes.byref(fa), None, s), "mlp_fwd")
+    torch.cuda.synchronize()
+    for k, x in fwd_bufs.items():
+        assert same(x, of_the_pass[k]), (k, int((x.view(torch.uint8) != of_the_pass[k].view(torch.uint8)).sum()))
+
+    g = torch.Generator().manual_seed(3)
+    grads = (torch.rand(R, 3, generator=g).to(d), torch.rand(R, generator=g).to(d), None, torch.rand(R, N, generator=g).to(d))
+    ba, gp, dc, dd, keep2 = ops.build_pass_bwd(prec, c, dr, t, None, 0.0, False, packed, c2f, save, out, grads, pose)
+    ws = keep2[0]
+    off = (ctypes.c_int64 * 8)()                          # {gradient area, d_sigma, d_z, d_len, partial blocks, dp, dv, total}
+    assert lib.sparf_debug_bwd_workspace(prec, R, N, int(pose), off) == 0 and off[0] == 0 and off[7] == ws.numel()
+    ws.fill_(FILL)
+    L.check(lib.sparf_pass_backward(ctypes.byref(ba), s), "bwd")
+    torch.cuda.synchronize()
+    ws_of_the_pass, gp_of_the_pass = ws.clone(), gp.clone()
+    assert written(ws_of_the_pass[:off[1]]) > off[1] // 8 and written(ws_of_the_pass[off[4]:]) > (off[7] - off[4]) // 8
+    ws[:off[1]].fill_(FILL)                               # gradient area: what which = 1 writes and which = 2 reads
+    ws[off[4]:].fill_(FILL)                               # partial blocks (which = 2), d point / d view encoding (which = 1)
+    gp.fill_(float("nan"))
+    L.check(lib.sparf_launch_kernel(1, ctypes.byref(fa), ctypes.byref(ba), s), "mlp_dgrad")
+    L.check(lib.sparf_launch_kernel(2, ctypes.byref(fa), ctypes.byref(ba), s), "wgrad")
+    torch.cuda.synchronize()
+    assert same(ws, ws_of_the_pass), int((ws != ws_of_the_pass).sum())
+    assert same(gp, gp_of_the_pass), int((gp.view(torch.int32) != gp_of_the_pass.view(torch.int32)).sum())

@@ -228,7 +228,7 @@ def test_gpu_ray_segments_equal_zeroed_gradients(R, N, seed, cuts, active, pose,
 @pytest.mark.gpu
 @pytest.mark.parametrize("R,first,pose", [(1600, 70, True), (1600, 64, False), (1100, 1, True), (600, 88, False)])
 def test_gpu_ray_segments_at_the_row_counts_where_the_data_gradient_kernel_changes_geometry(R, first, pose):
-    """The same property at the sizes where the bf16x3 data-gradient launch is planned per row count (api.hip x3_dgrad_rows8, round 6):
+    """The same property at the sizes where the bf16x3 data-gradient launch is planned per row count (pass_plan.h x3_dgrad_rows8, round 6):
     64 samples per ray with the first `first` rays inactive leave an active range that starts inside the pass (`row_begin` > 0, on a
     256-row tile boundary or not) and is, in turn, 1.5 rounds of 256-row tiles (the full round in 8 waves + the remainder in 4: two
     launches that must meet exactly at row_begin + 65 536), one-and-a-bit rounds, and less than one round (all in 4 waves).

@@ -24,7 +24,7 @@ def main(rev, tag):
     files = SOURCES + [h for h in HEADERS if not h.startswith("..")]
     for f in files:
         data = subprocess.check_output(["git", "show", f"{rev}:sparf_amd/csrc/{f}"], cwd=ROOT)
-        # api.hip includes "../../include/sparf_hip.h": give the old sources the header of THEIR revision
+        # the C ABI layer includes "../../include/sparf_hip.h": give the old sources the header of THEIR revision
         data = data.replace(b'"../../include/sparf_hip.h"', b'"sparf_hip.h"')
         open(os.path.join(src_dir, f), "wb").write(data)
     open(os.path.join(src_dir, "sparf_hip.h"), "wb").write(subprocess.check_output(["git", "show", f"{rev}:include/sparf_hip.h"], cwd=ROOT))

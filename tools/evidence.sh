@@ -22,7 +22,7 @@
 #   ab           per-kernel timings of variant libraries next to the default build (AB_TAGS, AB_PRECS)  -> r06_kernel_ab_<AB_NAME>.log
 #   fwdprobes    the same for the bf16x3 training forward (f0..f4 libraries over mlp_fwd_x3_train.hip)          -> r06_fwd_lap_table.log
 #   probe        which clock / power sensors the box offers + the calibration kernels (bench_telemetry.py)   -> r06_telemetry_probe.log
-#   geometry     bf16x3 data-gradient kernel, 8-wave vs 4-wave geometry by row count (api.hip x3_dgrad_waves) -> r06_dgrad_geometry.log
+#   geometry     bf16x3 data-gradient kernel, 8-wave vs 4-wave geometry by row count (pass_plan.h x3_dgrad_rows8) -> r06_dgrad_geometry.log
 #   smallstep    rocprofv3 kernel stats of a 512-ray step replayed as one hipGraph                    -> r06_r512_kernel_stats.csv
 #   registration joint pose-NeRF registration, oracle and HIP side by side (tests/tools/registration_run.py) -> r06_registration.json
 #   dgradprobes  wave-time accounting ("lap table") of the data-gradient kernel + its timing probes (variant libraries of tools/build_flag_variant.py) -> r06_dgrad_lap_table.log
@@ -129,7 +129,7 @@ PY
       grep -o '"value": [0-9.]*' gpurun_out/${TAG}_prof_r512.log | head -1
       python tools/prof_summary.py gpurun_out/prof/${TAG}_r512_results.db gpurun_out/${TAG}_r512_kernel_stats.csv; head -24 gpurun_out/${TAG}_r512_kernel_stats.csv | cut -c1-110,150-
       rm -rf gpurun_out/prof ;;
-    geometry)     # bf16x3 data-gradient kernel: 256-row (8 waves) vs 128-row (4 waves) workgroup tiles by row count (api.hip x3_dgrad_waves)
+    geometry)     # bf16x3 data-gradient kernel: 256-row (8 waves) vs 128-row (4 waves) workgroup tiles by row count (pass_plan.h x3_dgrad_rows8)
       for R in ${GEOM_RAYS:-512 1024 1536 2048 4096}; do for N in 64 192; do
         echo "== rays $R samples $N rows $((R*N))"
         KB_ONLY=dgrad timeout 300 python tools/kernel_bench.py bf16x3 $R $N 2>&1 | grep "^dgrad"
