@@ -15,6 +15,7 @@ import torch
 from . import camera
 from . import lib as L
 from . import ops
+from .batch_plan import Member, plan
 from .edict import EasyDict as edict, opt_get
 from .frequency_nerf import FrequencyEmbedder, NeRF, max_rows_per_call, pass_precision, shape_pass
 
@@ -29,16 +30,6 @@ def _as_float(x):
 def _deterministic(opt, mode):
     """whether the fine-sampling grid of a render in `mode` is the regular one (renderer.py:326-327)"""
     return mode not in ['train', 'test-optim'] or (not opt.nerf.sample_stratified)
-
-
-class _Shifted:
-    """rows [lo, hi) of a group addressed in a buffer that starts at group row `lo` (render_batch)"""
-
-    def __init__(self, buf, lo):
-        self.buf, self.lo = buf, lo
-
-    def __getitem__(self, s):
-        return self.buf[s.start - self.lo:s.stop - self.lo]
 
 
 class PendingRender(edict):
@@ -347,12 +338,15 @@ class Graph(torch.nn.Module):
             ray_idx = torch.randperm(H * W, device=self.device)[:opt.nerf.rand_rays // batch_size]
             ret = self.render(opt, pose, intr=data_dict.intr, ray_idx=ray_idx, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
             ret.ray_idx = ray_idx
-        elif opt.nerf.rand_rays:
-            ret = self.render_by_slices(opt, pose, intr=data_dict.intr, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
         else:
-            ret = self.render(opt, pose, intr=data_dict.intr, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
+            ret = self._render_all_rays(opt, pose, data_dict.intr, H, W, depth_range, iter, mode)
         ret.idx_img_rendered = torch.arange(start=0, end=batch_size).to(self.device)
         return ret
+
+    def _render_all_rays(self, opt, pose, intr, H, W, depth_range, iter, mode):
+        """every pixel of every image (no pixel or ray list given): in slices where the reference slices (opt.nerf.rand_rays set)"""
+        how = self.render_by_slices if opt.nerf.rand_rays else self.render
+        return how(opt, pose, intr=intr, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
 
     def render_image_at_specific_pose_and_rays(self, opt, data_dict, pose, intr, H, W, iter, pixels=None, ray_idx=None, mode='train'):
         """renderer.py:142-190."""
@@ -360,9 +354,7 @@ class Graph(torch.nn.Module):
         intr = intr.unsqueeze(0) if intr.dim() == 2 else intr
         depth_range = self._depth_range(opt, data_dict)
         if ray_idx is None and pixels is None:
-            if opt.nerf.rand_rays:
-                return self.render_by_slices(opt, pose, intr=intr, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
-            return self.render(opt, pose, intr=intr, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
+            return self._render_all_rays(opt, pose, intr, H, W, depth_range, iter, mode)
         ret = self._render_deferred(opt, pose, H, W, intr, pixels, ray_idx, depth_range, iter, mode)
         if ret is None:
             ret = self.render(opt, pose, intr=intr, pixels=pixels, ray_idx=ray_idx, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
@@ -385,26 +377,33 @@ class Graph(torch.nn.Module):
         that is not deferred, or by the next optimiser step."""
         hip = opt_get(opt, "hip")
         lazy = (hip is None or hip.get("lazy_batch", True)) if self._lazy_env is None else self._lazy_env != "0"
-        if not lazy or (hip is not None and (not hip.get("fused_render", True) or not hip.get("fused_rays", True))) \
+        if not lazy or (hip is not None and not hip.get("fused_rays", True)) \
                 or mode != "train" or not torch.is_grad_enabled() or opt.camera.ndc or intr.requires_grad:
             return None
         L.require_gpu(pose.device)
         B = pose.shape[0]
         R = ops.ray_request(B, pixels, ray_idx, H * W)[1]
-        Nc, Nf = int(opt.nerf.sample_intvs), int(opt.nerf.sample_intvs_fine or 0)
-        fine = self._fine_on(opt, iter)
-        n = B * R
-        prec, far = pass_precision(opt, Nc)
-        rows = n * (Nc + (Nf if fine else 0))
-        if n == 0 or rows > max_rows_per_call(prec, pose.device, need=rows, far=far):
+        route = self._fused_route(opt, B * R, iter, pose.device)
+        if route is None:
             return None
         if self._pending is not None and not self._pending.compatible(opt, iter, True):
             self.flush_pending()
         if self._pending is None:
             self._pending = _LazyBatch(self, opt, iter, True)
         q = dict(pose=pose, H=H, W=W, intr=intr, pixels=pixels, ray_idx=ray_idx, depth_range=depth_range, mode=mode,
-                 _draws=self._draw_randoms(opt, B, R, mode, fine))
+                 _draws=self._draw_randoms(opt, B, R, mode, route[0]))
         return self._pending.add(q)
+
+    def _fused_route(self, opt, n, iter, device):
+        """-> (fine, prec, far) of a render of n rays that takes the fused one-node route (_render_fused), or None where it does not:
+        `opt.hip.fused_render` off, no rays, or more sample rows in its passes than one launch set takes"""
+        hip = opt_get(opt, "hip")
+        if n == 0 or (hip is not None and not hip.get("fused_render", True)):
+            return None
+        fine = self._fine_on(opt, iter)
+        prec, far = pass_precision(opt, int(opt.nerf.sample_intvs))
+        rows = n * (int(opt.nerf.sample_intvs) + (int(opt.nerf.sample_intvs_fine or 0) if fine else 0))
+        return (fine, prec, far) if rows <= max_rows_per_call(prec, device, need=rows, far=far) else None
 
     def _draw_randoms(self, opt, B, R, mode, fine):
         """the random draws of one `render` call, in the reference's order (renderer.py:405-407 stratified jitter; frequency_nerf.py:191-192
@@ -442,10 +441,7 @@ class Graph(torch.nn.Module):
         H, W = data_dict.image.shape[-2:]
         depth_range = self._depth_range(opt, data_dict)
         if ray_idx is None and pixels is None:
-            if opt.nerf.rand_rays:
-                ret = self.render_by_slices(opt, pose, intr=intr, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
-            else:
-                ret = self.render(opt, pose, intr=intr, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
+            ret = self._render_all_rays(opt, pose, intr, H, W, depth_range, iter, mode)
         else:
             ret = self.render(opt, pose, intr=intr, pixels=pixels, ray_idx=ray_idx, mode=mode, H=H, W=W, depth_range=depth_range, iter=iter)
             ret.ray_idx = ray_idx
@@ -496,17 +492,13 @@ class Graph(torch.nn.Module):
         fine grid, fine density noise: renderer.py:405-407, frequency_nerf.py:191-192, renderer.py:439), same results bit for bit as
         the pass-by-pass path below it (tests/test_graph_gpu.py::test_fused_render_equals_pass_by_pass), which remains for renders
         larger than one launch set and for `opt.hip.fused_render = False`.  -> EasyDict, or None when the pass-by-pass path must run."""
-        hip = opt_get(opt, "hip")
-        if hip is not None and not hip.get("fused_render", True):
-            return None
         B, R = ray.shape[:2]
         Nc, Nf = int(opt.nerf.sample_intvs), int(opt.nerf.sample_intvs_fine or 0)
-        fine = self._fine_on(opt, iter)
         n = B * R
-        prec, far = pass_precision(opt, Nc)
-        if n == 0 or n * (Nc + (Nf if fine else 0)) > max_rows_per_call(prec, ray.device, need=n * (Nc + (Nf if fine else 0)), far=far):
+        route = self._fused_route(opt, n, iter, ray.device)
+        if route is None:
             return None
-        dev = ray.device
+        fine, prec, far = route
         dmin, dmax, scale, rd = self._range(depth_range)
         if draws is None:
             draws = self._draw_randoms(opt, B, R, mode, fine)
@@ -706,131 +698,86 @@ class Graph(torch.nn.Module):
         Returns the list of EasyDicts the separate calls would return."""
         L.require_gpu(self.device)
         self.flush_pending()
-        Nc = opt.nerf.sample_intvs
-        Nf = opt.nerf.sample_intvs_fine
-        reg = float(opt.nerf.density_noise_reg) if opt.nerf.density_noise_reg else 0.0
-        dev = self.device
-        fine_on = self._fine_on(opt, iter)
-        tomax_skip = self._to_max_fine_off(opt, iter)
+        if opt.camera.ndc:
+            raise NotImplementedError("camera.ndc is dead code in the reference (renderer.py:295 vs camera.py:439) and unsupported here")
+        Nc, Nf, dev = opt.nerf.sample_intvs, opt.nerf.sample_intvs_fine, self.device
         white_bg = bool(opt.nerf.setbg_opaque or opt.mask_img)
-
-        items = []
+        members = []
         for q in requests:
-            q = dict(q)
             B = q["pose"].shape[0]
             R = ops.ray_request(B, q.get("pixels"), q.get("ray_idx"), q["H"] * q["W"])[1]
-            items.append(dict(q=q, mode=q.get("mode"), to_max="depth_max" in q, B=B, R=R, n=B * R,
-                              nograd=bool(q.get("no_grad", False)) or not torch.is_grad_enabled()))
-
+            members.append(Member(B, R, "depth_max" in q, bool(q.get("no_grad", False)) or not torch.is_grad_enabled(), q.get("mode"),
+                                  q=q, draws=q.get("_draws") or {}))
         # precision of the passes: `render` requests carry the stratified coarse samples at the end of every ray (far-row routing
         # under inverse depth, frequency_nerf.pass_precision), render_to_max requests do not -- where the two differ they run as
-        # separate passes
-        prec_r = pass_precision(opt, Nc)
-        for nograd in (False, True):
-            # render requests first, render_to_max requests after them: each kind is then one contiguous row range
-            members = sorted([m for m in items if m["nograd"] == nograd], key=lambda m: m["to_max"])
-            if not members:
-                continue
-            Rtot = sum(m["n"] for m in members)
-            with torch.set_grad_enabled(not nograd):
-                # ray generation of the whole group into one (centres, directions) buffer, each request at its offset
+        # separate passes (batch_plan)
+        blocks = plan(members, Nc, Nf, self._fine_on(opt, iter), self._to_max_fine_off(opt, iter),
+                      float(opt.nerf.density_noise_reg) if opt.nerf.density_noise_reg else 0.0, L.MAX_SEGMENTS,
+                      prec_of=lambda to_max, N: pass_precision(opt, None, to_max_samples=N) if to_max else pass_precision(opt, Nc),
+                      cap_rows=lambda prec, need: max_rows_per_call(prec, dev, need=need),
+                      under=lambda nograd: torch.set_grad_enabled(not nograd))
+        for blk in blocks:
+            with torch.set_grad_enabled(not blk.nograd):
+                # ray generation of the whole block into one (centres, directions) buffer, each request at its offset
                 hip = opt_get(opt, "hip")
                 # (pixel lists that carry a gradient -- depth_cons_loss.py:291 -- take the per-request path: ops.RayGenMany sees its
                 # pixel lists as plain data)
                 fused = (hip is None or hip.get("fused_rays", True)) and not any(
-                    m["q"]["intr"].requires_grad or (m["q"].get("pixels") is not None and m["q"]["pixels"].requires_grad) for m in members)
-                off, specs = 0, []
-                for m in members:
-                    m["off"] = off
-                    off += m["n"]
-                    q = m["q"]
-                    px, ix = q.get("pixels"), q.get("ray_idx")
-                    if px is None and ix is None:
-                        ix = torch.arange(q["H"] * q["W"], device=dev)
-                    specs.append((q["intr"], px, None if px is not None else ix, q["W"]))
-                if opt.camera.ndc:
-                    raise NotImplementedError("camera.ndc is dead code in the reference (renderer.py:295 vs camera.py:439) and unsupported here")
+                    m.q["intr"].requires_grad or (m.q.get("pixels") is not None and m.q["pixels"].requires_grad) for m in blk.members)
                 if fused:
-                    rays = ops.ray_gen_many(specs, [m["q"]["pose"] for m in members])
+                    specs = []
+                    for m in blk.members:
+                        px, ix = m.q.get("pixels"), m.q.get("ray_idx")
+                        if px is None and ix is None:
+                            ix = torch.arange(m.q["H"] * m.q["W"], device=dev)
+                        specs.append((m.q["intr"], px, None if px is not None else ix, m.q["W"]))
+                    rays = ops.ray_gen_many(specs, [m.q["pose"] for m in blk.members])
                 else:       # PyTorch ray generation (intrinsics with a gradient): the per-request results, concatenated
-                    cr = [self._rays(opt, m["q"]["pose"], m["q"]["H"], m["q"]["W"], m["q"]["intr"], m["q"].get("pixels"), m["q"].get("ray_idx")) for m in members]
+                    cr = [self._rays(opt, m.q["pose"], m.q["H"], m.q["W"], m.q["intr"], m.q.get("pixels"), m.q.get("ray_idx")) for m in blk.members]
                     rays = torch.stack([torch.cat([c.reshape(-1, 3) for c, _ in cr]), torch.cat([r.reshape(-1, 3) for _, r in cr])])
-                t_all = torch.empty(Rtot, Nc, device=dev, dtype=torch.float32)
-                for m in members:                 # coarse depths, each request at its offset
-                    q, n, off = m["q"], m["n"], m["off"]
-                    m["pred"] = edict(origins=rays[0, off:off + n].view(m["B"], m["R"], 3), viewdirs=rays[1, off:off + n].view(m["B"], m["R"], 3))
-                    tv = t_all[off:off + n]
-                    if n > 0 and m["to_max"]:
-                        self._sample_depth_to_max(opt, m["B"], num_rays=m["R"], n_samples=Nc, H=q["H"], W=q["W"],
-                                                  depth_max=q["depth_max"], depth_min=q["depth_min"], mode=m["mode"], out=tv)
-                    elif n > 0:
-                        self._sample_depth(opt, m["B"], num_rays=m["R"], n_samples=Nc, H=q["H"], W=q["W"], depth_range=q["depth_range"],
-                                           mode=m["mode"], out=tv, jitter=(q.get("_draws") or {}).get("jitter"))
-                    m["t"] = tv.view(m["B"], m["R"], Nc, 1)
+                t_all = torch.empty(blk.rows, Nc, device=dev, dtype=torch.float32)
+                for m in blk.members:                 # coarse depths, each request at its offset
+                    q, rows = m.q, slice(m.off, m.off + m.n)
+                    m.pred = edict(origins=rays[0, rows].view(m.B, m.R, 3), viewdirs=rays[1, rows].view(m.B, m.R, 3))
+                    if m.n > 0 and m.to_max:
+                        self._sample_depth_to_max(opt, m.B, num_rays=m.R, n_samples=Nc, H=q["H"], W=q["W"],
+                                                  depth_max=q["depth_max"], depth_min=q["depth_min"], mode=m.mode, out=t_all[rows])
+                    elif m.n > 0:
+                        self._sample_depth(opt, m.B, num_rays=m.R, n_samples=Nc, H=q["H"], W=q["W"], depth_range=q["depth_range"],
+                                           mode=m.mode, out=t_all[rows], jitter=m.draws.get("jitter"))
+                for p in blk.coarse:
+                    self._batch_pass(p, rays, t_all, white_bg)
+                # render requests: resample + merge per request (own depth range / grid), into one [R, Nc+Nf] buffer; the fine network
+                # sees render_to_max requests on the SAME samples as the coarse one (renderer.py:583-592)
+                t_fine = torch.empty(blk.merged_rows, Nc + Nf, device=dev, dtype=torch.float32) if blk.merged_rows is not None else None
+                for m in blk.resample:
+                    dmin, dmax, _, rd = self._range(m.q["depth_range"])
+                    u_mid = m.draws.get("u_mid")
+                    with torch.no_grad():
+                        ops.sample_fine(m.pred["weights"].reshape(m.n, Nc), t_all[m.off:m.off + m.n],
+                                        u_mid if u_mid is not None else self._grid_midpoints(Nf, _deterministic(opt, m.mode)), dmin, dmax,
+                                        range_dev=rd, out=t_fine[m.off:m.off + m.n])
+                for p in blk.fine:
+                    self._batch_pass(p, rays, t_fine if p.merged else t_all, white_bg)
+        return [m.pred for m in members]
 
-                def run(net, group, t_buf, N, key_t, suffix):
-                    """one pass of `net` over the rays of `group` (contiguous members of this grad-mode block); more than
-                    L.MAX_SEGMENTS requests, or more sample rows than one launch set takes, run as consecutive passes"""
-                    if not group:
-                        return
-                    prec_m = pass_precision(opt, None, to_max_samples=N)     # (by value, under this group's grad mode)
-                    kinds = {m["to_max"] for m in group}
-                    if len(kinds) == 2 and prec_r != prec_m:          # render and render_to_max requests at different precisions
-                        run(net, [m for m in group if not m["to_max"]], t_buf, N, key_t, suffix)
-                        return run(net, [m for m in group if m["to_max"]], t_buf, N, key_t, suffix)
-                    prec, far = prec_m if group[0]["to_max"] else prec_r
-                    far = (far[0], far[1], net.packed(far[1])) if far is not None else None
-                    cap = max_rows_per_call(prec, dev, need=sum(m["n"] for m in group) * N) // N
-                    if len(group) > L.MAX_SEGMENTS or sum(m["n"] for m in group) > cap:
-                        part, rows = [], 0
-                        for m in group:
-                            if m["n"] > cap:
-                                raise L.SparfError(f"render_batch: one request of {m['n']} rays x {N} samples exceeds a launch set; render it with render()")
-                            if part and (len(part) == L.MAX_SEGMENTS or rows + m["n"] > cap):
-                                run(net, part, t_buf, N, key_t, suffix)
-                                part, rows = [], 0
-                            part.append(m)
-                            rows += m["n"]
-                        return run(net, part, t_buf, N, key_t, suffix)
-                    lo, hi = group[0]["off"], group[-1]["off"] + group[-1]["n"]
-                    segs = [(m["off"] - lo, m["n"], reg if (m["mode"] == "train" and reg > 0) else 0.0) for m in group]
-                    noise = None
-                    if any(s[2] > 0 for s in segs):      # frequency_nerf.py:191-192, per-request scale in the table
-                        pre = [(m["q"].get("_draws") or {}).get("noise_c" if suffix == "" else "noise_f") for m in group]
-                        if all(p is not None for p in pre):           # deferred calls: the draws they took when they were issued
-                            noise = pre[0] if len(pre) == 1 else torch.cat([p.reshape(m["n"], N) for p, m in zip(pre, group)])
-                        else:
-                            noise = torch.randn(hi - lo, N, device=dev)
-                    outs = ops.nerf_pass_segments(rays[0, lo:hi], rays[1, lo:hi], t_buf[lo:hi], noise, white_bg, prec, net.packed(prec),
-                                                  net.band_weights(), net.hip_params(), segs, far=far)
-                    for m, o in zip(group, outs):
-                        part = dict(shape_pass(o, m["B"], m["R"], N), t=m[key_t])
-                        m["out" + suffix] = part
-                        m["pred"].update({k + suffix: v for k, v in part.items()})
-
-                run(self.nerf, members, t_all, Nc, "t", "")
-                if fine_on:
-                    # render requests: resample + merge per request (own depth range / grid), into one [R, Nc+Nf] buffer; they are
-                    # laid first, render_to_max requests (fine network on the SAME samples, renderer.py:583-592) after them
-                    rend = [m for m in members if not m["to_max"]]
-                    tomx = [m for m in members if m["to_max"]]
-                    if rend:
-                        lo = rend[0]["off"]
-                        t_fine = torch.empty(sum(m["n"] for m in rend), Nc + Nf, device=dev, dtype=torch.float32)
-                        for m in rend:
-                            det = _deterministic(opt, m["mode"])
-                            dmin, dmax, _, rd = self._range(m["q"]["depth_range"])
-                            tv = t_fine[m["off"] - lo:m["off"] - lo + m["n"]]
-                            if m["n"] > 0:
-                                u_pre = (m["q"].get("_draws") or {}).get("u_mid")
-                                with torch.no_grad():
-                                    ops.sample_fine(m["out"]["weights"].reshape(m["n"], Nc), m["t"].reshape(m["n"], Nc),
-                                                    u_pre if u_pre is not None else self._grid_midpoints(Nf, det), dmin, dmax, range_dev=rd, out=tv)
-                            m["t_fine"] = tv.view(m["B"], m["R"], Nc + Nf, 1)
-                        run(self.nerf_fine, rend, _Shifted(t_fine, lo), Nc + Nf, "t_fine", "_fine")
-                    if tomx and not tomax_skip:
-                        run(self.nerf_fine, tomx, t_all, Nc, "t", "_fine")
-        return [m["pred"] for m in items]
+    def _batch_pass(self, p, rays, t_buf, white_bg):
+        """issue one planned pass (batch_plan.Pass) of a render_batch block: `rays`, `t_buf` are the block's ray and depth buffers"""
+        net = self.nerf_fine if p.fine else self.nerf
+        far = (p.far[0], p.far[1], net.packed(p.far[1])) if p.far is not None else None
+        noise = None
+        if p.noisy:      # frequency_nerf.py:191-192, per-request scale in the table
+            pre = [m.draws.get("noise_f" if p.fine else "noise_c") for m in p.members]
+            if all(z is not None for z in pre):           # deferred calls: the draws they took when they were issued
+                noise = pre[0] if len(pre) == 1 else torch.cat([z.reshape(m.n, p.N) for z, m in zip(pre, p.members)])
+            else:
+                noise = torch.randn(p.hi - p.lo, p.N, device=self.device)
+        outs = ops.nerf_pass_segments(rays[0, p.lo:p.hi], rays[1, p.lo:p.hi], t_buf[p.lo:p.hi], noise, white_bg, p.prec, net.packed(p.prec),
+                                      net.band_weights(), net.hip_params(), p.segs, far=far)
+        suffix = p.suffix
+        for m, o in zip(p.members, outs):
+            part = dict(shape_pass(o, m.B, m.R, p.N), t=t_buf[m.off:m.off + m.n].view(m.B, m.R, p.N, 1))
+            m.pred.update({k + suffix: v for k, v in part.items()})
 
     def sample_depth_diff_max_range_per_ray(self, opt, batch_size, n_samples, H, W, depth_min, depth_max, num_rays=None, mode=None):
         """t_i = (i+1)/n * (depth_max[b,r] - depth_min) + depth_min (renderer.py:595-624); metric only."""

@@ -374,6 +374,72 @@ def test_render_batch_more_requests_than_one_segment_table():
     assert max_rel(out["batch"][2], out["separate"][2].cpu()) < 2e-3
 
 
+def test_render_batch_cut_by_rows(monkeypatch):
+    """Five requests, 21 rays, where one launch set takes 96 sample rows: the coarse network (8 samples) runs over 12 + 9 rays, the
+    fine one (16 samples) over every request on its own -- same results as five separate calls, gradients included."""
+    import sparf_amd.frequency_nerf as fn
+    H, W, B = 10, 12, 2
+    opt = small_opt(nerf=dict(rand_rays=32))
+    pose, intr = ring_cameras(B, H=H, W=W)
+    K = intr.to(dev())
+    rs = np.random.RandomState(11)
+    idxs = [T(rs.randint(0, H * W, size=(3 + i % 4,))).to(dev()) for i in range(5)]
+    out = {}
+    for how in ("separate", "batch"):
+        if how == "batch":
+            for name in ("MAX_ROWS_PER_CALL", "MIN_ROWS_PER_CALL", "SAFE_ROWS"):
+                monkeypatch.setattr(fn, name, 8 * 12)
+            assert fn.max_rows_per_call(fn.get_precision(opt), dev(), need=21 * 8) == 8 * 12
+        graph = build(opt, 17)
+        pg = pose.to(dev()).requires_grad_(True)
+        reqs = [dict(pose=pg[i % B:i % B + 1], H=H, W=W, intr=K[i % B:i % B + 1], ray_idx=ix, depth_range=[1.2, 5.2], mode="val") for i, ix in enumerate(idxs)]
+        if how == "batch":
+            rets = graph.render_batch(opt, reqs, iter=None)
+        else:
+            rets = [graph.render(opt, q["pose"], H=H, W=W, intr=q["intr"], ray_idx=q["ray_idx"], depth_range=q["depth_range"], iter=None, mode="val") for q in reqs]
+        sum((i + 1) * r.rgb_fine.sum() + r.depth.sum() for i, r in enumerate(rets)).backward()
+        out[how] = (rets, pg.grad.clone(), graph.nerf_fine.mlp_feat[2].weight.grad.clone())
+    for a, b in zip(out["batch"][0], out["separate"][0]):
+        for k in ("rgb_fine", "depth", "t_fine", "weights_fine"):
+            assert torch.equal(a[k], b[k]), k
+    assert max_rel(out["batch"][1], out["separate"][1].cpu()) < 1e-4
+    assert max_rel(out["batch"][2], out["separate"][2].cpu()) < 2e-3
+
+
+def test_render_batch_runs_kinds_apart_when_precisions_differ():
+    """Inverse depth in bf16x3 under no_grad: a `render` pass routes the last 8 samples of every ray to fp32, a `render_to_max` pass
+    the tiles beyond depth 8.0 (frequency_nerf.pass_precision) -- two routes, so the two kinds of request run as separate passes and
+    every result is that of the separate call.  (far = (8, fp32) and (8.0, fp32) compare equal as tuples: the defaults once ran the
+    `render_to_max` rows of such a batch on the `render` route.)  Nothing is deferred under no_grad: the loss-facing wrappers, with
+    lazy batching left on, return the same."""
+    H, W, B = 10, 12, 3
+    opt = small_opt(nerf=dict(sample_intvs=32, sample_intvs_fine=32, sample_stratified=False, rand_rays=32, depth=dict(param="inverse", range=[1, 0])),
+                    hip=dict(precision="bf16x3"))
+    graph = build(opt, 23)
+    pose, intr = ring_cameras(B, H=H, W=W)
+    pg, K = pose.to(dev()), intr.to(dev())
+    rs = np.random.RandomState(3)
+    px = [T(rs.uniform(0, [W - 1, H - 1], size=(n, 2)).astype(np.float32)).to(dev()) for n in (24, 17, 21)]
+    dmax = T(rs.uniform(2.0, 14.0, size=(21,)).astype(np.float32)).to(dev())          # on both sides of opt.hip.far_depth = 8
+    data = data_dict(B, H, W, pose, intr)
+    with torch.no_grad():
+        reqs = [dict(pose=pg[0:1], H=H, W=W, intr=K[0:1], pixels=px[0], depth_range=opt.nerf.depth.range, mode="train"),
+                dict(pose=pg[2:3], H=H, W=W, intr=K[2:3], pixels=px[2], depth_min=opt.nerf.depth.range[0], depth_max=dmax, mode="train"),
+                dict(pose=pg[1:2], H=H, W=W, intr=K[1:2], pixels=px[1], depth_range=opt.nerf.depth.range, mode="train")]
+        bat = graph.render_batch(opt, reqs, iter=None)
+        sep = [graph.render_to_max(opt, q["pose"], H=H, W=W, intr=q["intr"], pixels=q["pixels"], depth_min=opt.nerf.depth.range[0], depth_max=dmax, iter=None, mode="train")
+               if "depth_max" in q else
+               graph.render(opt, q["pose"], H=H, W=W, intr=q["intr"], pixels=q["pixels"], depth_range=q["depth_range"], iter=None, mode="train") for q in reqs]
+        lazy = [graph.render_up_to_maxdepth_at_specific_pose_and_rays(opt, data, q["pose"][0], q["intr"][0], H, W, depth_max=dmax, iter=None, pixels=q["pixels"])
+                if "depth_max" in q else
+                graph.render_image_at_specific_pose_and_rays(opt, data, q["pose"][0], q["intr"][0], H, W, iter=None, pixels=q["pixels"]) for q in reqs]
+    assert graph.lazy_stats == dict(batches=0, requests=0)
+    for a, b, c in zip(bat, sep, lazy):
+        assert set(a.keys()) == set(b.keys()) == set(c.keys()) - {"ray_idx"} and "rgb_fine" in a.keys()
+        for k in a.keys():
+            assert torch.equal(a[k], b[k]) and torch.equal(a[k], c[k]), k
+
+
 def test_progress_write_through_data_takes_effect_immediately():
     """the trainer moves BARF c2f by progress.data.fill_(x) with no weight update in
     between (gradient accumulation, evaluation at several progress values).  Every render must use the
