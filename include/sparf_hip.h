@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SPARF_ABI_VERSION 6    /* 6: upstream gradients of EVERY output of a composite (depth_var, rgb_var, all_cumulated, density, rgb_samples) in
+#define SPARF_ABI_VERSION 7    /* 7: SPARF_SAVE_MASKS on a pass's precision id (ray-gradient-only passes); 6: upstream gradients of EVERY output of a composite (depth_var, rgb_var, all_cumulated, density, rgb_samples) in
                                   sparf_pass_bwd_t / sparf_segment_t; stand-alone sparf_composite_forward / _backward; 5: SPARF_SAVE_Q8 on a pass's precision id; 4: far rows of a pass (the last K samples of every ray through a second precision); 3: ray segments of a pass (sparf_segment_t), tile-block save areas without a 2^31-byte limit,
                                   device-side Adam step counter; 2: band weights per pass, photometric-loss workspace */
 #define SPARF_MAX_SEGMENTS 16
@@ -48,6 +48,16 @@ extern "C" {
  * of the plain precision bit for bit; the WEIGHT gradients carry ~1.75x the rounding error of the bf16 saves (measured,
  * DESIGN.md 6).  Not combinable with far rows (far_count > 0). */
 #define SPARF_SAVE_Q8 16
+/* Ray-gradient-only pass (ABI 7), OR-ed onto `prec` in the same four calls, any base precision: a pass whose only differentiable inputs
+ * are its rays (pose optimisation against frozen networks).  The forward with save != NULL leaves the ReLU mask words only:
+ * sparf_save_bytes(prec | SPARF_SAVE_MASKS, rows) = 9 216 B per 32-row tile (rows padded to 256).  sparf_pass_backward then requires d_center and
+ * d_dir (pose = 0 is an error, also from sparf_bwd_workspace_bytes), ignores grad_params (may be NULL), and runs the composite
+ * backward, the data gradient and the ray reduce -- no weight gradient; its workspace holds neither a gradient area nor partial
+ * blocks.  Every output of the pass and d_center / d_dir are those of the plain precision bit for bit; segments, the active ray range,
+ * accumulate_rays, density noise, every upstream gradient and far rows (far_ws: sparf_save_bytes(far_prec | SPARF_SAVE_MASKS, nrays * K))
+ * work as in a training pass.  Not combinable with SPARF_SAVE_Q8 (refused like an invalid precision id).  sparf_launch_kernel takes the
+ * flag for which = 0, 1, 3, 4 and returns non-zero for 2. */
+#define SPARF_SAVE_MASKS 32
 #define SPARF_N_LAYERS 10      /* mlp_feat.0..7, mlp_rgb.0..1 */
 #define SPARF_N_PARAMS 530052  /* weights + biases of one network, flat (W0,b0,W1,b1,...) */
 

@@ -6,7 +6,22 @@ and :247-272 (360-type data: metric depth, 1024 rays).  Reference
 `train_settings/*` configs can be passed to `Graph` unchanged; this module only
 exists so tests/bench/smoke can build an `opt` without the reference tree.
 """
-from .edict import EasyDict as edict
+from .edict import EasyDict as edict, opt_get
+
+
+# opt.hip.* keys of this renderer that change what a render computes or leaves behind, with their defaults (the reference's settings
+# files have no opt.hip: an absent key is its default).
+#   test_optim_rays_only: renders with mode == "test-optim" (the reference's test-time pose optimisation, joint_pose_nerf_trainer.py:381-406,
+#       whose optimiser holds nothing but the pose refinement) treat both networks as frozen: ray-gradient-only passes (ops.save_kind),
+#       no weight gradient.  Off by default: the unmodified loop never freezes the networks, and with the option on their `.grad` no longer
+#       receive what that loop accumulates into them (nothing in it reads them).
+HIP_DEFAULTS = dict(test_optim_rays_only=False)
+
+
+def hip_option(opt, key):
+    """opt.hip.<key> if the option tree has it, else its default (HIP_DEFAULTS)"""
+    hip = opt_get(opt, "hip")
+    return HIP_DEFAULTS[key] if hip is None else opt_get(hip, key, HIP_DEFAULTS[key])
 
 
 def default_opt(**over):

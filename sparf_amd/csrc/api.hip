@@ -38,16 +38,20 @@ static int launch_dgrad(const BwdPlan& b, hipStream_t s, int pin = 0) {
     const int prec = b.pp.base;
     const int64_t rows = b.row1 - b.row0;
     const int64_t rows8 = prec != PREC_X3 || b.pp.q8 || pin == 8 ? rows : pin == 4 ? 0 : b.rows8;
+    // (a ray-gradient-only pass: the kernels without dY stores over the masks-only save area, same geometries)
+    auto launch = [&](const MlpBwdArgs& a, int64_t n, int waves) {
+        return b.pp.masks ? launch_mlp_bwd_rays(prec, a, mlp_grid(prec, n), s, waves) : launch_mlp_bwd(prec, b.pose, b.pp.q8, a, mlp_grid(prec, n), s, waves);
+    };
     int rc = 0;
     if (rows8 > 0) {
         MlpBwdArgs a = b.m;
         a.rows = b.row0 + rows8;
-        rc = launch_mlp_bwd(prec, b.pose, b.pp.q8, a, mlp_grid(prec, rows8), s, 8);
+        rc = launch(a, rows8, 8);
     }
     if (!rc && rows8 < rows) {
         MlpBwdArgs a = b.m;
         a.row_begin = b.row0 + rows8;
-        rc = launch_mlp_bwd(prec, b.pose, b.pp.q8, a, mlp_grid(prec, rows - rows8), s, 4);
+        rc = launch(a, rows - rows8, 4);
     }
     return rc;
 }
@@ -163,14 +167,14 @@ int sparf_pass_forward(const sparf_pass_fwd_t* p, void* stream) {
     if (!rc) rc = launch_fwd(f.main, s);
     if (!rc && f.far_setup) rc = launch_ray_setup(f.far.prec, p->dir, p->nrays, p->c2f + 10, p->far_venc_ws, p->raylen, s);
     if (!rc && f.far_kind != FAR_NONE) rc = launch_fwd(f.far, s);
-    if (!rc && f.far_kind == FAR_ROWS && p->save) rc = launch_far_transplant(f.main.prec, p->far_ws, p->save, f.far.a.rows, p->far_count, p->nsamp, s);
+    if (!rc && f.far_kind == FAR_ROWS && p->save) rc = launch_far_transplant(f.main.prec, f.masks, p->far_ws, p->save, f.far.a.rows, p->far_count, p->nsamp, s);
     if (!rc) rc = launch_composite_fwd(f.c, s);
     return rc;
 }
 
 int64_t sparf_bwd_workspace_bytes(int prec, int nrays, int nsamp, int pose) {
     const PassPrec pp = pass_prec(prec);
-    if (!pp.ok || nrays < 0 || nsamp <= 0) return -1;
+    if (!pp.ok || nrays < 0 || nsamp <= 0 || (pp.masks && !pose)) return -1;
     return bwd_ws_layout(pp.af, nrays, nsamp, pose).total;
 }
 int sparf_pass_backward(const sparf_pass_bwd_t* p, void* stream) {
@@ -178,8 +182,9 @@ int sparf_pass_backward(const sparf_pass_bwd_t* p, void* stream) {
     int rc = plan_backward(p, false, &b);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    const bool masks = b.pp.masks;                            // ray-gradient-only: grad_params is not touched, no weight gradient runs
     if (b.rows == 0 || b.no_grad) {                           // empty batch, or no upstream gradient at all: zero results
-        if (hipMemsetAsync(p->grad_params, 0, (size_t)N_PARAMS * sizeof(float), s) != hipSuccess) return 2;
+        if (!masks && hipMemsetAsync(p->grad_params, 0, (size_t)N_PARAMS * sizeof(float), s) != hipSuccess) return 2;
         return b.rows && b.pose && !p->accumulate_rays ? zero_rays(p->d_center, p->d_dir, 0, p->nrays, s) : 0;
     }
     rc = launch_composite_bwd(b.c, s);
@@ -187,7 +192,7 @@ int sparf_pass_backward(const sparf_pass_bwd_t* p, void* stream) {
     // left, matrix-pipe-bound against HBM-bound -- was built and measured in round 4: bit-identical gradients, 3.5-13 % SLOWER than
     // this serial order at 2-8 chunks and 32-96 reserved CUs, profiles/r04e_overlap_schedule_sweep.log.  Removed.)
     if (!rc) rc = launch_dgrad(b, s);
-    if (!rc) rc = launch_wgrad(b.pp.base, b.pp.q8, b.g, b.split.nsplit, p->tables + kWsrcOff[b.pp.base], p->grad_params, s);
+    if (!rc && !masks) rc = launch_wgrad(b.pp.base, b.pp.q8, b.g, b.split.nsplit, p->tables + kWsrcOff[b.pp.base], p->grad_params, s);
     if (rc || !b.pose) return rc;
     // rays outside the active range receive no gradient: zero them unless the caller accumulates onto an earlier pass's
     if (!p->accumulate_rays && (zero_rays(p->d_center, p->d_dir, 0, b.ray0, s) || zero_rays(p->d_center, p->d_dir, b.ray1, p->nrays, s))) return 2;
@@ -268,6 +273,7 @@ int sparf_launch_kernel(int which, const sparf_pass_fwd_t* f, const sparf_pass_b
     BwdPlan b;
     const int rc = plan_backward(p, true, &b);
     if (rc || b.rows == 0) return rc;
+    if (which == 2 && b.pp.masks) return 1;                              // a ray-gradient-only pass has no weight gradient
     if (which == 2) return launch_wgrad(b.pp.base, b.pp.q8, b.g, b.split.nsplit, p->tables + kWsrcOff[b.pp.base], p->grad_params, s);
     return launch_dgrad(b, s, which == 1 ? 0 : which == 3 ? 8 : 4);      // 3 / 4: the bf16x3 kernel pinned to its 8-wave / 4-wave geometry
 }

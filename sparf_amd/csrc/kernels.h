@@ -36,7 +36,9 @@ static __host__ __device__ inline int64_t routed_row(int64_t r, int nsamp, int r
     const unsigned ur = (unsigned)r, q = ur / (unsigned)nsamp;
     return (int64_t)(q * (unsigned)row_stride + (unsigned)row_off + (ur - q * (unsigned)nsamp));
 }
-enum { FWD_INFER = 0, FWD_SAVE_PLANES = 1, FWD_SAVE_Q8 = 2 };      // what the forward kernel leaves behind for the backward
+// what the forward kernel leaves behind for the backward.  FWD_SAVE_MASKS: the ReLU mask words only, in an AREA_MASKS save area (layout.h):
+// all the data gradient of a ray-gradient-only pass reads
+enum { FWD_INFER = 0, FWD_SAVE_PLANES = 1, FWD_SAVE_Q8 = 2, FWD_SAVE_MASKS = 3 };
 int launch_mlp_fwd(int prec, int save, const MlpFwdArgs& a, int grid, hipStream_t stream);
 
 struct MlpBwdArgs {
@@ -57,6 +59,8 @@ struct MlpBwdArgs {
 // q8: the save / gradient areas are in the 8-bit format (layout.h AREA_Q8; bf16-operand modes)
 // waves: workgroup geometry of the bf16x3 kernel, 8 (256-row tiles, the default) or 4 (128-row tiles); other precisions have one geometry
 int launch_mlp_bwd(int prec, bool pose, bool q8, const MlpBwdArgs& a, int grid, hipStream_t stream, int waves = 8);
+// the data gradient of a ray-gradient-only pass (rays_bwd.hip): the pose variant over an AREA_MASKS save area, no dY stores (a.grad is not read)
+int launch_mlp_bwd_rays(int prec, const MlpBwdArgs& a, int grid, hipStream_t stream, int waves = 8);
 
 struct WgradArgs {
     const void* save;          // saved activations (X operands)
@@ -145,8 +149,9 @@ struct RayReduceArgs {
     int ray_base;
     int accumulate = 0;        // != 0: add to d_center / d_dir instead of overwriting them
 };
-// far rows of a pass: copy what the far (fp32) forward saved into the main (bf16-plane) save area, at the rows it stands for (ray_ops.hip)
-int launch_far_transplant(int main_prec, const void* far_area, void* main_area, int64_t frows, int far_count, int nsamp, hipStream_t s);
+// far rows of a pass: copy what the far (fp32) forward saved into the main (bf16-plane) save area, at the rows it stands for (ray_ops.hip);
+// masks: both areas are AREA_MASKS ones (a ray-gradient-only pass): the mask words only
+int launch_far_transplant(int main_prec, bool masks, const void* far_area, void* main_area, int64_t frows, int far_count, int nsamp, hipStream_t s);
 // d_dir = d_len * dir / |dir| (the stand-alone composite's only dependence on the ray: dist = delta * |ray|, frequency_nerf.py:302-308)
 int launch_len_to_dir(const float* dir, const float* raylen, const float* d_len, int nrays, float* d_dir, hipStream_t s);
 // prec < 0: raylen only (venc / c2f_view may be nullptr)

@@ -63,9 +63,13 @@ SP_HD constexpr int abytes_of(int prec) { return prec == PREC_BF16 ? 2 : 4; }
 // half the bytes of the bf16 planes for 1.75x their backward error (tests/tools/save_precision_study.py: a sum over rows
 // wants a linear grid with a per-row scale, not an 8-bit float).  Every function below that takes `prec` to size or address an
 // area takes an area format.
-enum { AREA_Q8 = 3 };
+// AREA_MASKS -- the format of a ray-gradient-only pass (sparf_hip.h SPARF_SAVE_MASKS), any precision: planes of ZERO bytes per element, so
+// that a tile block of the save area is its SB_COUNT mask KiB and nothing else, and the gradient area is empty.  The data gradient
+// reads the mask words only (mlp_bwd_impl.h); the planes and the dY vectors are the weight gradient's operands, which such a pass
+// does not run.
+enum { AREA_Q8 = 3, AREA_MASKS = 4 };
 SP_HD constexpr int area_format(int prec, bool q8) { return q8 ? (int)AREA_Q8 : prec; }
-SP_HD constexpr int plane_ebytes_of(int prec) { return prec == PREC_FP32 ? 4 : prec == AREA_Q8 ? 1 : 2; }
+SP_HD constexpr int plane_ebytes_of(int prec) { return prec == PREC_FP32 ? 4 : prec == AREA_Q8 ? 1 : prec == AREA_MASKS ? 0 : 2; }
 SP_HD constexpr int frag_bytes_of(int prec) { return prec == PREC_BF16 ? 1024 : prec == PREC_FP32 ? 256 : 2048; }
 
 // column of (q,h) inside a saved activation row: lanes write 16-byte chunks, the two
@@ -161,7 +165,7 @@ SP_HD constexpr int64_t grad_coloff(int b) {
 }
 // AREAS.  The save area (forward -> dgrad / wgrad) and the gradient area (dgrad -> wgrad) are
 // TILE-BLOCK-major: everything a 32-row tile owns is one contiguous block,
-//     save area : [tile32][buffer b][16-byte chunk c][row&31][CH elements] ... then SB_COUNT mask KiB
+//     save area : [tile32][buffer b][16-byte chunk c][row&31][CH elements] ... then SB_COUNT mask KiB   (AREA_MASKS: the mask KiB only)
 //     grad area : [tile32][buffer b][16-byte chunk c][row&31][CH elements]
 // i.e. inside a buffer exactly the register image of a wave (32 rows x CH-element chunks): every
 // 16-byte store / load instruction of the fused kernels covers 1 KiB of contiguous memory, and a

@@ -9,7 +9,8 @@
 // Math: SURVEY.md Appendix A "Backward" (autograd of
 // /root/reference/source/models/frequency_nerf.py:149-226).
 //
-// This file is the body of two translation units: mlp_bwd.hip (plane areas, every precision) and mlp_bwd_q8.hip (8-bit areas).
+// This file is the body of the translation units mlp_bwd*.hip (plane areas, one unit per precision / geometry; mlp_bwd_q8.hip: 8-bit areas)
+// and rays_bwd*.hip (ray-gradient-only passes: P = RaysOnly<...>, mlp_dev.h).
 #pragma once
 #include "kernels.h"
 #include "mlp_dev.h"
@@ -137,8 +138,12 @@ SP_DEV void bwd_layer_deferred(Pipe& pipe, int lane, const typename P::B* dy, Ep
 template <int PREC, bool POSE, class P = Policy<PREC>, bool Q8 = false>
 __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
     typedef typename P::B B;
-    constexpr int AF = area_format(PREC, Q8);
+    // RAYS (P = RaysOnly<...>): a ray-gradient-only pass -- the save area holds the mask words only (layout.h AREA_MASKS) and no dY leaves
+    // the kernel: nobody runs a weight gradient on it
+    constexpr bool RAYS = rays_only<P>::value != 0;
+    constexpr int AF = RAYS ? (int)AREA_MASKS : area_format(PREC, Q8);
     static_assert(!Q8 || sizeof(B) == 16, "8-bit gradient area: bf16 gradient operands only");
+    static_assert(!RAYS || (POSE && !Q8), "ray-gradient-only: the pose variant, no gradient area");
     constexpr int KJ = P::KJ, CH = P::CH, NW = P::NWAVES, G = P::G;
     constexpr int NB256 = 128 / KJ, NB128 = 64 / KJ;
 
@@ -190,7 +195,9 @@ __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
 #endif
                 constexpr int NST = decltype(nstc)::value, g = decltype(gc)::value, ng = decltype(ngc)::value;
                 constexpr int gb = decltype(gbc)::value, col0 = decltype(col0c)::value;
-                if constexpr (Q8) {
+                if constexpr (RAYS) {
+                    // (no gradient area)
+                } else if constexpr (Q8) {
                     constexpr int N16 = NST / 2, b0 = g * N16 / ng, b1 = (g + 1) * N16 / ng;
                     constexpr int part = col0 >= 256 ? 1 : 0;
                     constexpr int BASE = grad_buf_tile_off(AF, gb) + (col0 / 32) * 1024;

@@ -113,6 +113,12 @@ template <int W> struct PolicyX3DgradT {
 };
 typedef PolicyX3DgradT<8> PolicyX3Dgrad;          // the 256-row geometry (and the one the 8-bit-area kernels keep)
 typedef PolicyX3DgradT<4> PolicyX3DgradW4;
+// Data gradient of a ray-gradient-only pass (layout.h AREA_MASKS; rays_bwd*.hip): the arithmetic and geometry of policy P, carried in the
+// policy class -- mlp_bwd_kernel reads the trait below -- so that the kernel template keeps its parameter list.  The kernel then
+// addresses the masks-only save area and issues none of the dY stores.
+template <class P> struct RaysOnly : P {};
+template <class P> struct rays_only { enum { value = 0 }; };
+template <class P> struct rays_only<RaysOnly<P>> { enum { value = 1 }; };
 
 // ------------------------------------------------------------------ wave-time accounting (SP_PROF builds only)
 // tools/kernel_bench.py prints where wave 0 of workgroup 0 of the forward kernel spends its cycles

@@ -10,8 +10,8 @@
 // (compute_raw_density + forward), :47-69/:229-258 (encoding, c2f mask),
 // /root/reference/source/utils/camera.py:433-435 (p = c + r*t).
 //
-// This file is the body of six translation units (mlp_fwd_{bf16,fp32,x3}_{train,infer}.hip: one kernel each, compiled in
-// parallel -- as one unit the six kernel instantiations took many minutes).
+// This file is the body of one translation unit per kernel (mlp_fwd_{bf16,fp32,x3}_{train,train_q8,infer}.hip, rays_fwd_{bf16,fp32,x3}.hip),
+// compiled in parallel -- as one unit the kernel instantiations took many minutes.
 #pragma once
 #include <utility>
 
@@ -109,12 +109,13 @@ SP_DEV void fwd_layer(Pipe& pipe, const char* bias_h, int lane, const typename P
     });
 }
 
-// SAVEM: 0 inference (nothing saved), 1 training with plane saves, 2 training with 8-bit saves (layout.h AREA_Q8; bf16-operand modes)
+// SAVEM: 0 inference (nothing saved), 1 training with plane saves, 2 training with 8-bit saves (layout.h AREA_Q8; bf16-operand modes),
+// 3 the ReLU mask words only (layout.h AREA_MASKS; rays_fwd_*.hip): pushed and stored as in 1, none of the plane stores issued
 template <int PREC, int SAVEM>
 __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpFwdArgs a) {
     typedef Policy<PREC> P;
-    constexpr bool SAVE = SAVEM != 0, Q8 = SAVEM == 2;
-    constexpr int AF = area_format(PREC, Q8);          // format of the save area
+    constexpr bool SAVE = SAVEM != 0, Q8 = SAVEM == 2, PLANES = SAVEM == FWD_SAVE_PLANES;
+    constexpr int AF = SAVEM == FWD_SAVE_MASKS ? (int)AREA_MASKS : area_format(PREC, Q8);          // format of the save area
     static_assert(!Q8 || PREC != PREC_FP32, "8-bit saves: bf16-operand modes only");
     typedef typename P::B B;
     typedef typename P::stage_t stage_t;
@@ -385,7 +386,7 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
                 } else {
                     constexpr int c0 = g * NST / ng, c1 = (g + 1) * NST / ng;
                     constexpr int BASE = save_buf_tile_off(AF, sb) + (col0 / CH) * 512;
-                    if constexpr (SAVE && c1 > c0)
+                    if constexpr (PLANES && c1 > c0)
                         static_for<c1 - c0>([&](auto cc) { bstore_chunk<P, BASE, c0 + decltype(cc)::value>(srs, lvo, v); });
                 }
             };

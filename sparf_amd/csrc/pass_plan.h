@@ -13,14 +13,16 @@ static constexpr int64_t kPartialFloats = wpartial_floats();      // (compile ti
 
 static inline bool prec_ok(int p) { return p >= 0 && p < N_PREC; }
 // A pass's precision id may carry SPARF_SAVE_Q8 (sparf_hip.h): the arithmetic of `base`, save and gradient areas in the 8-bit format
-// (layout.h AREA_Q8); bf16-operand modes only
-struct PassPrec { int base; bool q8; int af; bool ok; };
+// (layout.h AREA_Q8); bf16-operand modes only.  Or SPARF_SAVE_MASKS: a ray-gradient-only pass of any base precision -- the save area
+// holds the ReLU mask words only (layout.h AREA_MASKS), the backward runs no weight gradient.  Not both.
+struct PassPrec { int base; bool q8, masks; int af; bool ok; };
 static inline PassPrec pass_prec(int p) {
     PassPrec r;
-    r.base = p & ~SPARF_SAVE_Q8;
+    r.base = p & ~(SPARF_SAVE_Q8 | SPARF_SAVE_MASKS);
     r.q8 = (p & SPARF_SAVE_Q8) != 0;
-    r.ok = prec_ok(r.base) && (!r.q8 || r.base == PREC_BF16 || r.base == PREC_X3);
-    r.af = area_format(r.ok ? r.base : 0, r.q8);
+    r.masks = (p & SPARF_SAVE_MASKS) != 0;
+    r.ok = prec_ok(r.base) && (!r.q8 || r.base == PREC_BF16 || r.base == PREC_X3) && !(r.q8 && r.masks);
+    r.af = r.masks ? (int)AREA_MASKS : area_format(r.ok ? r.base : 0, r.q8);
     return r;
 }
 // one launch set takes up to 2^27 sample rows (the per-row outputs are indexed with 32-bit element offsets);
@@ -115,7 +117,7 @@ static inline BwdWs bwd_ws_layout(int af, int nrays, int nsamp, int pose) {     
     w.d_sigma = o; o += align256(rows * 4);
     w.d_z = o; o += align256(rows * 12);
     w.d_len = o; o += align256((int64_t)nrays * 4);
-    w.nsplit = wgrad_splits(rows).nsplit;
+    w.nsplit = af == AREA_MASKS ? 0 : wgrad_splits(rows).nsplit;          // (a ray-gradient-only pass: no gradient area above, no partial blocks)
     w.partial = o; o += align256((int64_t)w.nsplit * kPartialFloats * 4);
     w.dp = o; if (pose) o += align256(rows * 12);
     w.dv = o; if (pose) o += align256(rows * 128);
@@ -170,13 +172,14 @@ static inline bool seg_table(int nseg, const sparf_segment_t* seg, int nrays, bo
 
 // ---- forward
 struct FwdLaunch {                   // one launch_mlp_fwd: on mlp_grid(prec, a.rows) workgroups
-    int prec, save;                  // save: FWD_INFER / FWD_SAVE_PLANES / FWD_SAVE_Q8
+    int prec, save;                  // save: FWD_INFER / FWD_SAVE_PLANES / FWD_SAVE_Q8 / FWD_SAVE_MASKS
     MlpFwdArgs a;
 };
 enum { FAR_NONE = 0, FAR_ROWS, FAR_TILES };
 struct FwdPlan {
     FwdLaunch main, far;             // far: only if far_kind
     int far_kind;
+    bool masks;                      // ray-gradient-only pass: far rows leave and transplant mask words only
     bool far_setup;                  // a launch_ray_setup of its own for the far launch, into far_venc_ws (the per-ray view-encoding rows
                                      // are laid out per precision: element type AND 16-byte-chunk order, ray_setup_kernel)
     CompositeFwdArgs c;
@@ -200,7 +203,8 @@ static inline int plan_forward(const sparf_pass_fwd_t* p, FwdPlan* f) {
     if (!far_ok(p->far_count, p->far_prec, p->nsamp, prec)) return 1;
     if (p->far_count && (!p->far_packed || (p->save != nullptr && !p->far_ws) || (p->far_prec != prec && !p->far_venc_ws))) return 1;
     if (p->far_count == -1 && p->save != nullptr) return 1;            // tile routing: inference passes only
-    f->main = FwdLaunch{prec, !p->save ? FWD_INFER : pp.q8 ? FWD_SAVE_Q8 : FWD_SAVE_PLANES, mlp_fwd_args(p)};
+    f->masks = pp.masks;
+    f->main = FwdLaunch{prec, !p->save ? FWD_INFER : pp.q8 ? FWD_SAVE_Q8 : pp.masks ? FWD_SAVE_MASKS : FWD_SAVE_PLANES, mlp_fwd_args(p)};
     f->far_kind = p->far_count == 0 ? FAR_NONE : p->far_count == -1 ? FAR_TILES : FAR_ROWS;
     f->far_setup = f->far_kind != FAR_NONE && p->far_prec != prec;
     f->far = FwdLaunch{p->far_prec, FWD_INFER, f->main.a};
@@ -224,7 +228,8 @@ static inline int plan_forward(const sparf_pass_fwd_t* p, FwdPlan* f) {
         a.nsamp = p->far_count;
         a.row_stride = p->nsamp;
         a.row_off = p->nsamp - p->far_count;
-        if (p->save) { a.save = p->far_ws; f->far.save = FWD_SAVE_PLANES; }
+        // (a ray-gradient-only pass: the far precision's masks-only kernel, far_ws an AREA_MASKS area of nrays * K rows)
+        if (p->save) { a.save = p->far_ws; f->far.save = pp.masks ? FWD_SAVE_MASKS : FWD_SAVE_PLANES; }
     }
     f->c = CompositeFwdArgs{p->nrays, p->nsamp, p->t, p->sigma_raw, p->noise, p->noise_scale, p->rgb_samples, p->raylen, p->white_bg,
                             p->weights, p->density, p->rgb, p->depth, p->opacity, p->depth_var, p->rgb_var, p->all_cumulated, {}};
@@ -234,7 +239,7 @@ static inline int plan_forward(const sparf_pass_fwd_t* p, FwdPlan* f) {
 // ---- backward
 struct BwdPlan {
     PassPrec pp;
-    bool pose;                       // ray gradients wanted (d_center and d_dir)
+    bool pose;                       // ray gradients wanted (d_center and d_dir); always, in a ray-gradient-only pass (pp.masks)
     int64_t rows;                    // of the whole pass; 0: empty batch, nothing below is filled
     int ray0, ray1;                  // active rays [ray0, ray1) and their rows [row0, row1): what the kernels run over
     int64_t row0, row1;
@@ -254,12 +259,13 @@ static inline int plan_backward(const sparf_pass_bwd_t* p, bool whole_pass, BwdP
     const PassPrec pp = b->pp = pass_prec(p->prec);
     if (!pp.ok || p->nrays < 0 || p->nsamp <= 0) return 1;
     const int64_t rows = b->rows = (int64_t)p->nrays * p->nsamp;
-    if (p->nrays == 0) return p->grad_params ? 0 : 1;         // empty batch: zero parameter gradients
+    if (p->nrays == 0) return p->grad_params || pp.masks ? 0 : 1;         // empty batch: zero parameter gradients (ray-gradient-only: nothing)
     if (!rows_ok(rows)) return 4;
     const bool pose = b->pose = p->d_center != nullptr;
     if (pose != (p->d_dir != nullptr)) return 1;
+    if (pp.masks && !pose) return 1;                          // a ray-gradient-only pass without ray gradients
     if (!p->center || !p->dir || !p->t || !p->packed || !p->c2f || !p->tables || !p->save || !p->raylen || !p->sigma_raw ||
-        !p->rgb_samples || !p->weights || !p->ws || !p->grad_params)
+        !p->rgb_samples || !p->weights || !p->ws || (!p->grad_params && !pp.masks))
         return 1;
     const BwdWs& w = b->ws = bwd_ws_layout(pp.af, p->nrays, p->nsamp, pose);
     char* ws = (char*)p->ws;

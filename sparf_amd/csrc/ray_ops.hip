@@ -438,10 +438,11 @@ __global__ void __launch_bounds__(64) ray_reduce_kernel(RayReduceArgs a) {
 // to row g % 32 of tile g / 32 of the main (bf16-plane) save area, its mask words to that row's two lane slots.  One workgroup per
 // 32-row far tile.  Layouts (layout.h): a buffer is [16-byte chunk][row & 31][CH elements] in `pos` order, CH = 4 (fp32) / 8 (bf16):
 // bf16 chunk 2a + h = slots q = 8a .. 8a+7 of half h = fp32 chunks 4a + h (q % 8 < 4) and 4a + 2 + h.
+// masks != 0: a ray-gradient-only pass -- both areas are AREA_MASKS ones (the far launch ran the fp32 masks-only forward): the mask words only.
 __global__ void __launch_bounds__(256) far_transplant_kernel(const char* __restrict__ far_area, char* __restrict__ main_area, int64_t frows,
-                                                             int K, int nsamp, int64_t main_tile_bytes, int main_mask_off) {
-    constexpr int64_t FT = save_tile_bytes(PREC_FP32);
-    constexpr int FMASK = save_mask_tile_off(PREC_FP32, 0);
+                                                             int K, int nsamp, int64_t main_tile_bytes, int main_mask_off, int masks) {
+    const int64_t FT = masks ? save_tile_bytes(AREA_MASKS) : save_tile_bytes(PREC_FP32);
+    const int FMASK = masks ? save_mask_tile_off(AREA_MASKS, 0) : save_mask_tile_off(PREC_FP32, 0);
     constexpr int NCH8 = SAVE_COLS / 8;                      // 16-byte bf16 chunks per row over all buffers (buffer widths are multiples of 32)
     const int64_t ft = blockIdx.x;
     const char* src_tile = far_area + ft * FT;
@@ -457,7 +458,7 @@ __global__ void __launch_bounds__(256) far_transplant_kernel(const char* __restr
     }
     __syncthreads();
     typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    for (int i = threadIdx.x; i < 32 * NCH8; i += blockDim.x) {
+    for (int i = threadIdx.x; i < (masks ? 0 : 32 * NCH8); i += blockDim.x) {
         const int j = i & 31, c8g = i >> 5;                  // far row, bf16 chunk counted over the whole saved row
         const int64_t drow = dst_row_off[j];
         if (drow < 0) continue;
@@ -490,12 +491,12 @@ __global__ void __launch_bounds__(256) far_transplant_kernel(const char* __restr
     }
 }
 
-int launch_far_transplant(int main_prec, const void* far_area, void* main_area, int64_t frows, int far_count, int nsamp, hipStream_t s) {
+int launch_far_transplant(int main_prec, bool masks, const void* far_area, void* main_area, int64_t frows, int far_count, int nsamp, hipStream_t s) {
     if (frows <= 0) return 0;
     if (main_prec == PREC_FP32) return 1;       // bf16-plane save areas only (bf16, bf16x3: its head planes)
     const int64_t ntiles = (frows + 31) / 32;
     hipLaunchKernelGGL(far_transplant_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, (const char*)far_area, (char*)main_area, frows, far_count, nsamp,
-                       save_tile_bytes(main_prec), save_mask_tile_off(main_prec, 0));
+                       save_tile_bytes(masks ? (int)AREA_MASKS : main_prec), save_mask_tile_off(masks ? (int)AREA_MASKS : main_prec, 0), masks ? 1 : 0);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

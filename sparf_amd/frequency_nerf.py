@@ -21,6 +21,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from .config import hip_option
 from .edict import opt_get
 
 COMPOSITE_KEYS = ("rgb", "rgb_var", "depth", "depth_var", "opacity", "weights", "all_cumulated")
@@ -341,8 +342,11 @@ class NeRF(torch.nn.Module):
             noise = torch.randn(B * R, N, device=ray.device)       # frequency_nerf.py:192
         c, d = center.reshape(B * R, 3), ray.reshape(B * R, 3)
         nz = noise.reshape(B * R, N) if use_noise else None
+        packed = self.packed(prec, params)
+        if mode == "test-optim" and bool(hip_option(opt, "test_optim_rays_only")):       # (config.HIP_DEFAULTS; renderer._nets_frozen)
+            params = [p.detach() for p in params]                                        # no route for a parameter gradient
         args = (float(opt.nerf.density_noise_reg) if use_noise else 0.0, bool(opt.nerf.setbg_opaque or opt.mask_img),
-                prec, self.packed(prec, params), self.band_weights(), params)
+                prec, packed, self.band_weights(), params)
         max_rays = max(1, max_rows_per_call(prec, ray.device, need=B * R * N, far=far) // N)
         if B * R <= max_rays:
             out = ops.nerf_pass(c, d, t, nz, *args, far=far)

@@ -23,6 +23,28 @@ def _f32(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+# what the forward of a pass leaves behind for its backward
+SAVE_NONE, SAVE_FULL, SAVE_MASKS = "none", "full", "masks"
+
+
+def save_kind(grad_mode, rays_need_grad, params_need_grad, prec):
+    """(grad mode at the call site, the rays need a gradient, any parameter of THIS pass's network needs one, precision id of the pass)
+    -> SAVE_NONE: nothing differentiable, the inference kernel runs; SAVE_MASKS: a ray-gradient-only pass (sparf_hip.h
+    SPARF_SAVE_MASKS) -- the rays are the pass's only differentiable inputs: pose optimisation against a frozen network; SAVE_FULL: a
+    training pass.  The '+q8' precisions keep the full route.  Decided per pass: a frozen coarse network next to a trainable fine one is a
+    mixed render."""
+    if not grad_mode or not (rays_need_grad or params_need_grad):
+        return SAVE_NONE
+    if rays_need_grad and not params_need_grad and not (prec & L.SAVE_Q8):
+        return SAVE_MASKS
+    return SAVE_FULL
+
+
+def pass_prec_of(prec, kind):
+    """the precision id a pass of save kind `kind` hands the C ABI"""
+    return prec | L.SAVE_MASKS if kind == SAVE_MASKS else prec
+
+
 def pack_weights(params, prec, out=None):
     """params: 20 tensors (W0,b0,...,W9,b9) in nn.Linear layout on one cuda device.
     Returns the packed uint8 blob consumed by the pass kernels."""
@@ -164,7 +186,7 @@ def _set_far(a, far, save, prec, R, N, dev):
     """Far rows of the forward struct `a`: far = (K, far_prec, far_packed) -- the last K samples of every ray also run through far_prec
     (sparf_hip.h "far rows") -- or (threshold, ...) with a FLOAT threshold: far TILES by value, inference passes only (far_count = -1).
     save: whether the pass saves for a backward; what the far launch saves is transplanted into the pass's save area by the call, its own
-    area is scratch.  -> what to keep alive until the stream has run the call (the caching allocator hands it out again in stream order)."""
+    area is scratch (of the far precision's masks-only format when `prec` carries SAVE_MASKS).  -> what to keep alive until the stream has run the call (the caching allocator hands it out again in stream order)."""
     k, fprec, fpacked = far
     far_ws = None
     if isinstance(k, float):
@@ -175,12 +197,12 @@ def _set_far(a, far, save, prec, R, N, dev):
         if not 0 < k < N:
             raise L.SparfError(f"far rows: 0 < K < samples per ray, got K = {k} of {N}")
         if save:
-            far_ws = torch.empty(L.load().sparf_save_bytes(fprec, R * k), dtype=torch.uint8, device=dev)
+            far_ws = torch.empty(L.load().sparf_save_bytes(fprec | (prec & L.SAVE_MASKS), R * k), dtype=torch.uint8, device=dev)
             a.far_ws = far_ws.data_ptr()
         a.far_count = int(k)
     a.far_prec, a.far_packed = int(fprec), fpacked.data_ptr()
     keep = [fpacked, far_ws]
-    if fprec != prec:              # the view-encoding rows are laid out per precision: the far launch gets its own
+    if fprec != L.base_prec(prec):              # the view-encoding rows are laid out per precision: the far launch gets its own
         fvenc = torch.empty(_venc_bytes(fprec, R), dtype=torch.uint8, device=dev)
         a.far_venc_ws = fvenc.data_ptr()
         keep.append(fvenc)
@@ -190,6 +212,7 @@ def _set_far(a, far, save, prec, R, N, dev):
 def build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, segs=None, far=None):
     """Allocate outputs and fill the C struct of sparf_pass_forward.  Returns
     (struct, outputs dict, save buffer(s) or None, scratch list to keep alive).
+    prec: the pass precision id, with SAVE_MASKS for a ray-gradient-only pass (pass_prec_of): the save area is then the mask words only.
     segs: optional [(ray0, nrays, noise_scale), ...] ray segments (include/sparf_hip.h sparf_segment_t).
     far: optional (K | threshold, far_prec, far_packed): far rows (_set_far)."""
     lib = L.load()
@@ -217,12 +240,13 @@ def build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save,
 def build_pass_bwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, fwd_out, grads, pose, segs=None):
     """Allocate workspace / results and fill the C struct of sparf_pass_backward.
     grads = (g_rgb, g_depth, g_opacity, g_weights[, g_depth_var, g_rgb_var, g_all_cumulated, g_density, g_rgb_samples]), any may be
-    None; with `segs` a list of such tuples, one per ray segment (each tensor covering only its segment's rays)."""
+    None; with `segs` a list of such tuples, one per ray segment (each tensor covering only its segment's rays).
+    prec with SAVE_MASKS (a ray-gradient-only pass): no parameter gradient is computed, the returned `gp` is None."""
     lib = L.load()
     dev = c.device
     R, N = tt.shape
     ws = torch.empty(lib.sparf_bwd_workspace_bytes(prec, R, N, int(pose)), dtype=torch.uint8, device=dev)
-    gp = torch.empty(L.N_PARAMS, dtype=torch.float32, device=dev)
+    gp = torch.empty(L.N_PARAMS, dtype=torch.float32, device=dev) if not (prec & L.SAVE_MASKS) else None
     dc = torch.empty(R, 3, dtype=torch.float32, device=dev) if pose else None
     dd = torch.empty(R, 3, dtype=torch.float32, device=dev) if pose else None
     gseg = [[_f32(g) if g is not None else None for g in gt] for gt in grads] if segs else None
@@ -278,7 +302,11 @@ class NerfPass(torch.autograd.Function):
         # needs_input_grad ignores the caller's grad mode (and forward() itself always runs with
         # grad disabled): `grad_mode` = torch.is_grad_enabled() at the call site.  Without it
         # nothing is saved and the inference kernel runs.
-        need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
+        kind = save_kind(bool(grad_mode), ctx.needs_input_grad[0] or ctx.needs_input_grad[1], any(ctx.needs_input_grad[12:]), prec)
+        if kind == SAVE_NONE and bool(grad_mode) and any(ctx.needs_input_grad):
+            kind = SAVE_FULL                      # (some other input carries a gradient flag: as before)
+        need_grad = kind != SAVE_NONE
+        prec = pass_prec_of(prec, kind)
         ctx.set_materialize_grads(False)          # absent upstream gradients arrive as None, not as zero tensors
         a, out, save, _keep = build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, need_grad, segs=segs, far=far)
         with L.on(dev):
@@ -633,14 +661,19 @@ class RenderFn(torch.autograd.Function):
         plan = _plan(R, Nc, Nf if fine else 0)
         c, d = _contig32(center), _contig32(dirs)
         need_grad = bool(cfg["grad"]) and any(ctx.needs_input_grad)
+        # per pass: a network none of whose parameters wants a gradient (theta is None) under rays that do = a ray-gradient-only pass
+        rays_grad = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        kinds = [save_kind(need_grad, rays_grad, ctx.needs_input_grad[14], cfg["prec_c"]), save_kind(need_grad, rays_grad, ctx.needs_input_grad[15], cfg["prec_f"])]
+        kinds = [SAVE_FULL if (need_grad and k == SAVE_NONE) else k for k in kinds]       # (a pass without differentiable inputs next to one with: as before)
         ctx.set_materialize_grads(False)
         arenas = (torch.empty(plan.total[0], dtype=torch.float32, device=dev), torch.empty(plan.total[1], dtype=torch.float32, device=dev))
         bases = (arenas[0].data_ptr(), arenas[1].data_ptr())
         A = lambda name: bases[plan.off[name][2]] + 4 * plan.off[name][0]
         stream = L.stream_ptr(dev)
-        passes = [("c", Nc, cfg["prec_c"], cfg["far_c"], packed_c, far_packed_c, noise_c, prog_c)]
+        precs = [pass_prec_of(cfg["prec_c"], kinds[0]), pass_prec_of(cfg["prec_f"], kinds[1])]
+        passes = [("c", Nc, precs[0], cfg["far_c"], packed_c, far_packed_c, noise_c, prog_c)]
         if fine:
-            passes.append(("f", Nc + Nf, cfg["prec_f"], cfg["far_f"], packed_f, far_packed_f, noise_f, prog_f))
+            passes.append(("f", Nc + Nf, precs[1], cfg["far_f"], packed_f, far_packed_f, noise_f, prog_f))
         saves, keep = [], []
         c2f_off = None if cfg["c2f"] is not None else c2f_weights(None, None, dev).data_ptr()     # no masking: the constant vector of the device
         with L.on(dev):
@@ -681,7 +714,7 @@ class RenderFn(torch.autograd.Function):
         ctx.mark_non_differentiable(*outs[9::10])
         if need_grad:
             ctx.save_for_backward(c, d, arenas[0], arenas[1], noise_c, noise_f, packed_c, packed_f, *saves)
-            ctx.cfg, ctx.plan, ctx.npass, ctx.c2f_off = cfg, plan, len(passes), c2f_off
+            ctx.cfg, ctx.plan, ctx.npass, ctx.c2f_off, ctx.precs = cfg, plan, len(passes), c2f_off, precs
         return tuple(outs)
 
     @staticmethod
@@ -695,11 +728,12 @@ class RenderFn(torch.autograd.Function):
         A = lambda name: bases[plan.off[name][2]] + 4 * plan.off[name][0]
         pose = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         c2f_of = lambda tag: ctx.c2f_off if ctx.c2f_off is not None else A(tag + "c2f")       # the vector the forward of that pass was given
-        passes = [("c", Nc, cfg["prec_c"], packed_c, noise_c, c2f_of("c"), saves[0], g[0:9])]
+        passes = [("c", Nc, ctx.precs[0], packed_c, noise_c, c2f_of("c"), saves[0], g[0:9])]
         if npass == 2:
-            passes.append(("f", Nc + Nf, cfg["prec_f"], packed_f, noise_f, c2f_of("f"), saves[1], g[10:19]))
+            passes.append(("f", Nc + Nf, ctx.precs[1], packed_f, noise_f, c2f_of("f"), saves[1], g[10:19]))
         active = [p for p in passes if any(x is not None for x in p[7])]
-        gp = torch.empty(2, L.N_PARAMS, dtype=torch.float32, device=dev)
+        full = {p[0] for p in active if not (p[2] & L.SAVE_MASKS)}          # the passes that compute a parameter gradient
+        gp = torch.empty(2, L.N_PARAMS, dtype=torch.float32, device=dev) if full else None
         rays = torch.empty(2, R, 3, dtype=torch.float32, device=dev) if pose else None
         stream = L.stream_ptr(dev)
         keep = []
@@ -714,14 +748,13 @@ class RenderFn(torch.autograd.Function):
                                    noise_scale=cfg["noise_scale"] if noise is not None else 0.0, white_bg=cfg["white_bg"], packed=packed.data_ptr(),
                                    c2f=c2f, tables=tables.data_ptr(), save=save.data_ptr(), raylen=A(tag + "raylen"), sigma_raw=A(tag + "sigma_raw"),
                                    rgb_samples=A(tag + "rgb_samples"), weights=A(tag + "weights"), ws=ws.data_ptr(),
-                                   grad_params=gp.data_ptr() + (0 if tag == "c" else 4 * L.N_PARAMS), d_center=P(rays[0]) if pose else None,
+                                   grad_params=gp.data_ptr() + (0 if tag == "c" else 4 * L.N_PARAMS) if tag in full else None, d_center=P(rays[0]) if pose else None,
                                    d_dir=P(rays[1]) if pose else None, accumulate_rays=0 if first else 1, **{k: P(x) for k, x in zip(_GRAD_FIELDS, gs)})
                 L.check(lib.sparf_pass_backward(ctypes.byref(a), stream), "sparf_pass_backward")
                 keep += [ws, gs]
                 first = False
-        tags = {p[0] for p in active}
-        g_c = gp[0] if "c" in tags else None
-        g_f = gp[1] if ("f" in tags and npass == 2) else None
+        g_c = gp[0] if "c" in full else None
+        g_f = gp[1] if ("f" in full and npass == 2) else None
         if not active:
             rays = None
         return (rays[0] if (rays is not None and ctx.needs_input_grad[0]) else None, rays[1] if (rays is not None and ctx.needs_input_grad[1]) else None,

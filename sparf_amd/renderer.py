@@ -16,6 +16,7 @@ from . import camera
 from . import lib as L
 from . import ops
 from .batch_plan import Member, plan
+from .config import hip_option
 from .edict import EasyDict as edict, opt_get
 from .frequency_nerf import FrequencyEmbedder, NeRF, max_rows_per_call, pass_precision, shape_pass
 
@@ -25,6 +26,12 @@ _LOGGED_MODES = set()
 
 def _as_float(x):
     return float(x.item()) if torch.is_tensor(x) else float(x)
+
+
+def _nets_frozen(opt, mode):
+    """opt.hip.test_optim_rays_only (config.HIP_DEFAULTS: off): a render of the test-time pose optimisation hands the networks' parameters to no
+    autograd node -- their .grad stay untouched, the passes run ray-gradient-only"""
+    return mode == "test-optim" and bool(hip_option(opt, "test_optim_rays_only"))
 
 
 def _deterministic(opt, mode):
@@ -505,7 +512,9 @@ class Graph(torch.nn.Module):
         jitter, noise_c, u_mid, noise_f, use_noise = draws["jitter"], draws["noise_c"], draws["u_mid"], draws["noise_f"], draws["use_noise"]
         pc = self.nerf.hip_params()
         pf = self.nerf_fine.hip_params() if fine else None
-        grad = torch.is_grad_enabled()
+        # theta = None: no parameter of that network wants a gradient (requires_grad_(False), or opt.hip.test_optim_rays_only under
+        # mode "test-optim") -- with rays that do, ops.RenderFn then runs that pass ray-gradient-only (ops.save_kind)
+        grad = torch.is_grad_enabled() and not _nets_frozen(opt, mode)
         theta_c = self.nerf.flat_params(pc) if grad else None
         theta_f = self.nerf_fine.flat_params(pf) if (grad and fine) else None
         fprec = far[1] if far is not None else None
@@ -746,7 +755,7 @@ class Graph(torch.nn.Module):
                         self._sample_depth(opt, m.B, num_rays=m.R, n_samples=Nc, H=q["H"], W=q["W"], depth_range=q["depth_range"],
                                            mode=m.mode, out=t_all[rows], jitter=m.draws.get("jitter"))
                 for p in blk.coarse:
-                    self._batch_pass(p, rays, t_all, white_bg)
+                    self._batch_pass(p, rays, t_all, white_bg, opt)
                 # render requests: resample + merge per request (own depth range / grid), into one [R, Nc+Nf] buffer; the fine network
                 # sees render_to_max requests on the SAME samples as the coarse one (renderer.py:583-592)
                 t_fine = torch.empty(blk.merged_rows, Nc + Nf, device=dev, dtype=torch.float32) if blk.merged_rows is not None else None
@@ -758,10 +767,10 @@ class Graph(torch.nn.Module):
                                         u_mid if u_mid is not None else self._grid_midpoints(Nf, _deterministic(opt, m.mode)), dmin, dmax,
                                         range_dev=rd, out=t_fine[m.off:m.off + m.n])
                 for p in blk.fine:
-                    self._batch_pass(p, rays, t_fine if p.merged else t_all, white_bg)
+                    self._batch_pass(p, rays, t_fine if p.merged else t_all, white_bg, opt)
         return [m.pred for m in members]
 
-    def _batch_pass(self, p, rays, t_buf, white_bg):
+    def _batch_pass(self, p, rays, t_buf, white_bg, opt=None):
         """issue one planned pass (batch_plan.Pass) of a render_batch block: `rays`, `t_buf` are the block's ray and depth buffers"""
         net = self.nerf_fine if p.fine else self.nerf
         far = (p.far[0], p.far[1], net.packed(p.far[1])) if p.far is not None else None
@@ -772,8 +781,11 @@ class Graph(torch.nn.Module):
                 noise = pre[0] if len(pre) == 1 else torch.cat([z.reshape(m.n, p.N) for z, m in zip(pre, p.members)])
             else:
                 noise = torch.randn(p.hi - p.lo, p.N, device=self.device)
+        params = net.hip_params()
+        if p.members and all(_nets_frozen(opt if opt is not None else self.opt, m.mode) for m in p.members):          # (what routes the parameter gradient: nothing)
+            params = [x.detach() for x in params]
         outs = ops.nerf_pass_segments(rays[0, p.lo:p.hi], rays[1, p.lo:p.hi], t_buf[p.lo:p.hi], noise, white_bg, p.prec, net.packed(p.prec),
-                                      net.band_weights(), net.hip_params(), p.segs, far=far)
+                                      net.band_weights(), params, p.segs, far=far)
         suffix = p.suffix
         for m, o in zip(p.members, outs):
             part = dict(shape_pass(o, m.B, m.R, p.N), t=t_buf[m.off:m.off + m.n].view(m.B, m.R, p.N, 1))

@@ -8,7 +8,7 @@
 
 Reads the gfx950 code object out of sparf_amd/csrc/build/<unit>.o (compiles the unit into a scratch directory when there is no
 object newer than its sources) and prints, per kernel: MFMAs, all other instructions, s_nop, v_readlane_b32 / v_writelane_b32
-(scalars parked in VGPR lanes), v_pk_add_f32, and the code-object notes (registers, spills, scratch, LDS).  The tile body of these
+(scalars parked in VGPR lanes), v_pk_add_f32, 16-byte vector buffer stores, and the code-object notes (registers, spills, scratch, LDS).  The tile body of these
 kernels is fully unrolled, so the static counts are per tile and wave; the rest of the kernel (prologue, the 15-iteration
 encoding loop counted once) is a few hundred instructions.  tests/test_kernel_stream_cpu.py pins the figures of the two kernels."""
 import collections
@@ -75,7 +75,8 @@ def count_stream(lines):
     c = collections.Counter(ops[:last + 1])
     mfma = sum(v for k, v in c.items() if k.startswith("v_mfma"))
     return {"mfma": mfma, "other": sum(c.values()) - mfma, "s_nop": c["s_nop"], "v_readlane_b32": c["v_readlane_b32"],
-            "v_writelane_b32": c["v_writelane_b32"], "v_pk_add_f32": c["v_pk_add_f32"]}
+            "v_writelane_b32": c["v_writelane_b32"], "v_pk_add_f32": c["v_pk_add_f32"],
+            "buffer_store_dwordx4": c["buffer_store_dwordx4"]}          # 16-byte vector buffer stores: the save / gradient-area traffic of a tile
 
 
 def listings_of(co):
