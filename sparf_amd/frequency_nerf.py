@@ -14,15 +14,13 @@ The sample -> encode -> MLP -> sigma/rgb -> composite chain runs as one fused pa
 (renderer.py:304-309), are thin views over it.
 """
 import math
-import os
 
 import numpy as np
 import torch
 
 from . import lib as L
 from . import ops
-from .config import hip_option
-from .edict import opt_get
+from .config import DEFAULT_FAR_DEPTH, DEFAULT_FAR_SAMPLES, DEFAULT_PRECISION, hip_option      # noqa: F401  (the defaults are read from here: bench.py)
 
 COMPOSITE_KEYS = ("rgb", "rgb_var", "depth", "depth_var", "opacity", "weights", "all_cumulated")
 MAX_ROWS_PER_CALL = 1 << 23          # upper limit of sample rows per pass launch when activations are saved (a memory bound, not an addressing one)
@@ -81,25 +79,23 @@ def max_rows_per_call(prec=None, device=None, need=None, far=None):
     return max(MIN_ROWS_PER_CALL, rows // 8192 * 8192)
 
 
-DEFAULT_PRECISION = "bf16x3"         # the ONE default: what an unmodified run_trainval.py gets, and what bench.py measures
-DEFAULT_FAR_SAMPLES = 8
+def white_bg(opt):
+    """whether what a ray does not hit is white (frequency_nerf.py:331-332)"""
+    return bool(opt.nerf.setbg_opaque or opt.mask_img)
 
 
-def _hip_get(opt):
-    hip = opt_get(opt, "hip")
-    return lambda k, d=None: d if hip is None else opt_get(hip, k, d)
+def density_noise_on(opt, mode):
+    """whether a pass in `mode` perturbs its raw density (frequency_nerf.py:191-192)"""
+    return bool(opt.nerf.density_noise_reg) and mode == "train"
 
 
 def precision_name(opt):
     """opt.hip.precision, else $SPARF_PRECISION, else DEFAULT_PRECISION ('bf16x3': the fastest mode whose outputs stay
     within 1e-4 of the reference; 'fp32' = exact fp32 MFMA arithmetic, the reference's own floor; 'bf16' = throughput mode)."""
-    name = _hip_get(opt)("precision") or os.environ.get("SPARF_PRECISION") or DEFAULT_PRECISION
+    name = hip_option(opt, "precision")
     if name not in L.PREC_IDS:
         raise ValueError(f"unknown precision {name!r} (choose from {sorted(L.PREC_IDS)})")
     return name
-
-
-DEFAULT_FAR_DEPTH = 8.0
 
 
 def pass_precision(opt, n_coarse=None, to_max_samples=None):
@@ -127,7 +123,6 @@ def pass_precision(opt, n_coarse=None, to_max_samples=None):
     Anything else (explicit points, the public forward_samples, render_to_max with gradients) runs on the fp32 kernels as a whole,
     as all inverse-depth passes did in round 3.
     opt.hip.inverse_depth_precision: 'routed' (default) | 'fp32' (whole passes, round 3) | 'bf16x3' (no correction, ~1e-4)."""
-    get = _hip_get(opt)
     name = precision_name(opt)
     # '+q8' (8-bit save and gradient areas, lib.SAVE_Q8) changes what a training pass keeps for its backward, not its arithmetic: the
     # routing below is that of the plain mode, and a pass with far ROWS keeps plane saves (the far rows' activations are transplanted
@@ -135,16 +130,16 @@ def pass_precision(opt, n_coarse=None, to_max_samples=None):
     q8 = L.SAVE_Q8 if name.endswith("+q8") else 0
     name = name[:-3] if q8 else name
     if name == "bf16x3" and opt.nerf.depth.param == "inverse":
-        how = get("inverse_depth_precision") or os.environ.get("SPARF_INVERSE_DEPTH_PRECISION") or "routed"
+        how = hip_option(opt, "inverse_depth_precision")
         if how not in ("routed", "fp32", "bf16x3"):
             raise ValueError(f"opt.hip.inverse_depth_precision must be 'routed', 'fp32' or 'bf16x3', not {how!r}")
         if how == "bf16x3":
             return L.PREC_X3 | q8, None
-        K = int(get("far_samples") or os.environ.get("SPARF_FAR_SAMPLES") or DEFAULT_FAR_SAMPLES)
+        K = hip_option(opt, "far_samples")
         if how == "routed" and n_coarse is not None and min(K, n_coarse - 1) > 0:
             return L.PREC_X3, (min(K, n_coarse - 1), L.PREC_FP32)
         if how == "routed" and to_max_samples is not None and to_max_samples % 32 == 0 and not torch.is_grad_enabled():
-            return L.PREC_X3, (float(get("far_depth") or os.environ.get("SPARF_FAR_DEPTH") or DEFAULT_FAR_DEPTH), L.PREC_FP32)
+            return L.PREC_X3, (hip_option(opt, "far_depth"), L.PREC_FP32)
         return L.PREC_FP32, None
     return L.PREC_IDS[name] | q8, None
 
@@ -337,16 +332,15 @@ class NeRF(torch.nn.Module):
         prec, far = pass_precision(opt, n_coarse, to_max_samples=N if to_max else None)
         params = self.hip_params()
         far = (far[0], far[1], self.packed(far[1], params)) if far is not None else None
-        use_noise = bool(opt.nerf.density_noise_reg) and mode == "train"
+        use_noise = density_noise_on(opt, mode)
         if use_noise and noise is None:
             noise = torch.randn(B * R, N, device=ray.device)       # frequency_nerf.py:192
         c, d = center.reshape(B * R, 3), ray.reshape(B * R, 3)
         nz = noise.reshape(B * R, N) if use_noise else None
         packed = self.packed(prec, params)
-        if mode == "test-optim" and bool(hip_option(opt, "test_optim_rays_only")):       # (config.HIP_DEFAULTS; renderer._nets_frozen)
+        if mode == "test-optim" and bool(hip_option(opt, "test_optim_rays_only")):       # (config.HIP_KEYS; renderer._nets_frozen)
             params = [p.detach() for p in params]                                        # no route for a parameter gradient
-        args = (float(opt.nerf.density_noise_reg) if use_noise else 0.0, bool(opt.nerf.setbg_opaque or opt.mask_img),
-                prec, packed, self.band_weights(), params)
+        args = (float(opt.nerf.density_noise_reg) if use_noise else 0.0, white_bg(opt), prec, packed, self.band_weights(), params)
         max_rays = max(1, max_rows_per_call(prec, ray.device, need=B * R * N, far=far) // N)
         if B * R <= max_rays:
             out = ops.nerf_pass(c, d, t, nz, *args, far=far)
@@ -379,8 +373,7 @@ class NeRF(torch.nn.Module):
             return pred_dict
         rgb_s, dens = pred_dict["rgb_samples"], pred_dict["density_samples"]
         B, R, N = dens.shape
-        out = ops.composite(ray.reshape(B * R, 3), dens.reshape(B * R, N), rgb_s.reshape(B * R, N, 3), depth_samples.reshape(B * R, N),
-                            bool(opt.nerf.setbg_opaque or opt.mask_img))
+        out = ops.composite(ray.reshape(B * R, 3), dens.reshape(B * R, N), rgb_s.reshape(B * R, N, 3), depth_samples.reshape(B * R, N), white_bg(opt))
         pred_dict.update(shape_pass(out, B, R, N))
         return pred_dict
 

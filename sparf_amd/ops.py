@@ -4,6 +4,7 @@ every FLOP of the hot path runs in the HIP kernels behind the C ABI.
 """
 import ctypes
 import math
+from collections import namedtuple
 from ctypes import c_void_p
 
 import torch
@@ -40,9 +41,22 @@ def save_kind(grad_mode, rays_need_grad, params_need_grad, prec):
     return SAVE_FULL
 
 
+def pass_save_kind(grad_mode, rays_need_grad, params_need_grad, prec, any_need_grad):
+    """save_kind of one pass of a call, `any_need_grad`: any input of the call needs a gradient -- a pass with no differentiable input
+    of its own next to one that has (a frozen network under rays without a gradient beside a trainable one; some other input that
+    carries a gradient flag) takes the full route"""
+    kind = save_kind(grad_mode, rays_need_grad, params_need_grad, prec)
+    return SAVE_FULL if (kind == SAVE_NONE and grad_mode and any_need_grad) else kind
+
+
 def pass_prec_of(prec, kind):
     """the precision id a pass of save kind `kind` hands the C ABI"""
     return prec | L.SAVE_MASKS if kind == SAVE_MASKS else prec
+
+
+def has_param_grad(prec):
+    """whether the backward of a pass with precision id `prec` computes a parameter gradient: not a ray-gradient-only one"""
+    return not (prec & L.SAVE_MASKS)
 
 
 def pack_weights(params, prec, out=None):
@@ -144,8 +158,9 @@ def sample_fine(weights, t_coarse, u_mid, dmin, dmax, want_unsorted=False, range
     return out, tf
 
 
-def _segments(segs, grads=None):
-    """ctypes array of sparf_segment_t from [(ray0, nrays, noise_scale), ...] (+ per-segment upstream gradients)"""
+def _segments(a, segs, grads=None):
+    """the segment table of the pass struct `a`: a ctypes array of sparf_segment_t from [(ray0, nrays, noise_scale), ...] (+ per-segment
+    upstream gradients), set on `a` and returned for the caller to keep alive"""
     if len(segs) > L.MAX_SEGMENTS:
         raise L.SparfError(f"at most {L.MAX_SEGMENTS} ray segments per pass")
     arr = (L.Segment * len(segs))()
@@ -153,6 +168,7 @@ def _segments(segs, grads=None):
         arr[i].ray0, arr[i].nrays, arr[i].noise_scale = int(r0), int(n), float(ns)
         for k, x in zip(_GRAD_FIELDS, grads[i] if grads is not None else ()):
             setattr(arr[i], k, x.data_ptr() if x is not None else None)
+    a.nseg, a.seg = len(segs), arr
     return arr
 
 
@@ -164,7 +180,7 @@ def _venc_bytes(prec, R):
 def _fill_pass_fwd(*, prec, nrays, nsamp, center, dir, t, noise, noise_scale, white_bg, packed, c2f, save, venc_ws,
                    raylen, sigma_raw, rgb_samples, density, weights, rgb, depth, opacity, depth_var, rgb_var, all_cumulated):
     """sparf_pass_fwd_t from addresses (int | None) and scalars: the ONE place that names its fields, all required keywords -- a field
-    a route forgets is a TypeError, not a null pointer.  Segment table and far rows are set on the result (build_pass_fwd, _set_far)."""
+    a route forgets is a TypeError, not a null pointer.  Segment table and far rows are set on the result (prepare_pass_fwd)."""
     return L.PassFwd(prec=prec, nrays=nrays, nsamp=nsamp, center=center, dir=dir, t=t, noise=noise, noise_scale=float(noise_scale),
                      white_bg=int(bool(white_bg)), packed=packed, c2f=c2f, save=save, venc_ws=venc_ws, raylen=raylen, sigma_raw=sigma_raw,
                      rgb_samples=rgb_samples, density=density, weights=weights, rgb=rgb, depth=depth, opacity=opacity, depth_var=depth_var,
@@ -182,87 +198,105 @@ def _fill_pass_bwd(*, prec, nrays, nsamp, center, dir, t, noise, noise_scale, wh
                      g_all_cumulated=g_all_cumulated, g_density=g_density, g_rgb_samples=g_rgb_samples, accumulate_rays=accumulate_rays)
 
 
-def _set_far(a, far, save, prec, R, N, dev):
-    """Far rows of the forward struct `a`: far = (K, far_prec, far_packed) -- the last K samples of every ray also run through far_prec
-    (sparf_hip.h "far rows") -- or (threshold, ...) with a FLOAT threshold: far TILES by value, inference passes only (far_count = -1).
-    save: whether the pass saves for a backward; what the far launch saves is transplanted into the pass's save area by the call, its own
-    area is scratch (of the far precision's masks-only format when `prec` carries SAVE_MASKS).  -> what to keep alive until the stream has run the call (the caching allocator hands it out again in stream order)."""
-    k, fprec, fpacked = far
-    far_ws = None
-    if isinstance(k, float):
-        if save or N % 32 != 0:
-            raise L.SparfError("far tiles by value: inference passes with a multiple of 32 samples per ray only")
-        a.far_count, a.far_thr = -1, k
-    else:
-        if not 0 < k < N:
-            raise L.SparfError(f"far rows: 0 < K < samples per ray, got K = {k} of {N}")
-        if save:
-            far_ws = torch.empty(L.load().sparf_save_bytes(fprec | (prec & L.SAVE_MASKS), R * k), dtype=torch.uint8, device=dev)
-            a.far_ws = far_ws.data_ptr()
-        a.far_count = int(k)
-    a.far_prec, a.far_packed = int(fprec), fpacked.data_ptr()
-    keep = [fpacked, far_ws]
-    if fprec != L.base_prec(prec):              # the view-encoding rows are laid out per precision: the far launch gets its own
-        fvenc = torch.empty(_venc_bytes(fprec, R), dtype=torch.uint8, device=dev)
-        a.far_venc_ws = fvenc.data_ptr()
-        keep.append(fvenc)
-    return keep
+def _addr(x):
+    return x.data_ptr() if x is not None else None
+
+
+def _contig32(g):
+    return g if (g.dtype is torch.float32 and g.is_contiguous()) else g.detach().to(torch.float32).contiguous()
+
+
+def prepare_pass_fwd(prec, R, N, dev, *, save, noise_scale, white_bg, segs=None, far=None, **addr):
+    """Everything of a sparf_pass_forward call but the pass's inputs and results, whose addresses (int | None) the caller hands over as
+    `addr`: center, dir, t, noise, packed, c2f and the eleven results of _PASS_F32.  -> (struct, save area | None, what to keep alive
+    until the stream has run the call: the caching allocator hands it out again in stream order).
+    prec: the pass precision id, with SAVE_MASKS for a ray-gradient-only pass (pass_save_kind, pass_prec_of): the save area is then the
+    mask words only.  save: whether the pass saves for a backward.
+    segs: optional [(ray0, nrays, noise_scale), ...] ray segments (include/sparf_hip.h sparf_segment_t).
+    far: optional (K, far_prec, address of the far_prec packed weights) -- the last K samples of every ray also run through far_prec
+    (sparf_hip.h "far rows"); what the far launch saves is transplanted into the pass's save area by the call, its own area is scratch
+    (of the far precision's masks-only format when `prec` carries SAVE_MASKS) -- or (threshold, ...) with a FLOAT threshold: far TILES
+    by value, inference passes only (far_count = -1)."""
+    lib = L.load()
+    save_buf = torch.empty(lib.sparf_save_bytes(prec, R * N), dtype=torch.uint8, device=dev) if save else None
+    venc = torch.empty(_venc_bytes(prec, R), dtype=torch.uint8, device=dev)
+    a = _fill_pass_fwd(prec=prec, nrays=R, nsamp=N, noise_scale=noise_scale, white_bg=white_bg, save=_addr(save_buf), venc_ws=venc.data_ptr(), **addr)
+    keep = [venc]
+    if segs:
+        keep.append(_segments(a, segs))
+    if far is not None:
+        k, fprec, fpacked = far
+        if isinstance(k, float):
+            if save or N % 32 != 0:
+                raise L.SparfError("far tiles by value: inference passes with a multiple of 32 samples per ray only")
+            a.far_count, a.far_thr = -1, k
+        else:
+            if not 0 < k < N:
+                raise L.SparfError(f"far rows: 0 < K < samples per ray, got K = {k} of {N}")
+            if save:
+                far_ws = torch.empty(lib.sparf_save_bytes(fprec | (prec & L.SAVE_MASKS), R * k), dtype=torch.uint8, device=dev)
+                a.far_ws = far_ws.data_ptr()
+                keep.append(far_ws)
+            a.far_count = int(k)
+        a.far_prec, a.far_packed = int(fprec), fpacked
+        if fprec != L.base_prec(prec):              # the view-encoding rows are laid out per precision: the far launch gets its own
+            fvenc = torch.empty(_venc_bytes(fprec, R), dtype=torch.uint8, device=dev)
+            a.far_venc_ws = fvenc.data_ptr()
+            keep.append(fvenc)
+    return a, save_buf, keep
+
+
+def prepare_pass_bwd(prec, R, N, dev, *, grads, grad_params, d_center, d_dir, noise_scale, white_bg, accumulate_rays=0, segs=None, **addr):
+    """Everything of a sparf_pass_backward call but the addresses (int | None) of what its forward read and left behind, handed over as
+    `addr` (center, dir, t, noise, packed, c2f, save, raylen, sigma_raw, rgb_samples, weights), and of its results: grad_params
+    [N_PARAMS] (ignored by a ray-gradient-only pass -- `prec` with SAVE_MASKS, has_param_grad: it computes none), d_center, d_dir [R,3]
+    (both None: no ray gradients; accumulate_rays = 1: the call adds to them).  -> (struct, what to keep alive).
+    grads = (g_rgb, g_depth, g_opacity, g_weights[, g_depth_var, g_rgb_var, g_all_cumulated, g_density, g_rgb_samples]) tensors, any
+    may be None; with `segs` a list of such tuples, one per ray segment (each tensor covering only its segment's rays).  They are made
+    dense float32 here."""
+    dense = lambda gt: [_contig32(g) if g is not None else None for g in gt]
+    gseg = [dense(gt) for gt in grads] if segs else None
+    gs = dense(grads) if not segs else []       # (segmented: the table carries them)
+    gs += [None] * (9 - len(gs))
+    ws = torch.empty(L.load().sparf_bwd_workspace_bytes(prec, R, N, int(d_center is not None)), dtype=torch.uint8, device=dev)
+    tables = L.tables_device(L.base_prec(prec), dev)
+    a = _fill_pass_bwd(prec=prec, nrays=R, nsamp=N, noise_scale=noise_scale, white_bg=white_bg, tables=tables.data_ptr(), ws=ws.data_ptr(),
+                       grad_params=grad_params if has_param_grad(prec) else None, d_center=d_center, d_dir=d_dir, accumulate_rays=accumulate_rays,
+                       **addr, **{k: _addr(g) for k, g in zip(_GRAD_FIELDS, gs)})
+    keep = [ws, tables] + gs
+    if segs:
+        keep += [_segments(a, segs, gseg), gseg]
+    return a, keep
 
 
 def build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, segs=None, far=None):
-    """Allocate outputs and fill the C struct of sparf_pass_forward.  Returns
-    (struct, outputs dict, save buffer(s) or None, scratch list to keep alive).
-    prec: the pass precision id, with SAVE_MASKS for a ray-gradient-only pass (pass_prec_of): the save area is then the mask words only.
-    segs: optional [(ray0, nrays, noise_scale), ...] ray segments (include/sparf_hip.h sparf_segment_t).
-    far: optional (K | threshold, far_prec, far_packed): far rows (_set_far)."""
-    lib = L.load()
+    """Allocate outputs and fill the C struct of sparf_pass_forward (prepare_pass_fwd).  Returns
+    (struct, outputs dict, save buffer or None, scratch list to keep alive).
+    far: optional (K | threshold, far_prec, far_packed tensor)."""
     dev = c.device
     R, N = tt.shape
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     out = dict(raylen=f(R), sigma_raw=f(R, N), rgb_samples=f(R, N, 3), density=f(R, N), weights=f(R, N), rgb=f(R, 3),
                depth=f(R), opacity=f(R), depth_var=f(R), rgb_var=f(R), all_cumulated=f(R))
-    save_buf = torch.empty(lib.sparf_save_bytes(prec, R * N), dtype=torch.uint8, device=dev) if save else None
-    venc = torch.empty(_venc_bytes(prec, R), dtype=torch.uint8, device=dev)
-    a = _fill_pass_fwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=tt.data_ptr(),
-                       noise=nz.data_ptr() if nz is not None else None, noise_scale=noise_scale, white_bg=white_bg, packed=packed.data_ptr(),
-                       c2f=c2f.data_ptr(), save=save_buf.data_ptr() if save_buf is not None else None, venc_ws=venc.data_ptr(),
-                       **{k: v.data_ptr() for k, v in out.items()})
-    keep = [venc]
-    if segs:
-        sa = _segments(segs)
-        a.nseg, a.seg = len(segs), sa
-        keep.append(sa)
-    if far is not None:
-        keep += _set_far(a, far, save, prec, R, N, dev)
+    a, save_buf, keep = prepare_pass_fwd(prec, R, N, dev, save=save, noise_scale=noise_scale, white_bg=white_bg, segs=segs,
+                                         far=(far[0], far[1], far[2].data_ptr()) if far is not None else None, center=c.data_ptr(),
+                                         dir=d.data_ptr(), t=tt.data_ptr(), noise=_addr(nz), packed=packed.data_ptr(), c2f=c2f.data_ptr(),
+                                         **{k: v.data_ptr() for k, v in out.items()})
     return a, out, save_buf, keep
 
 
 def build_pass_bwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, fwd_out, grads, pose, segs=None):
-    """Allocate workspace / results and fill the C struct of sparf_pass_backward.
-    grads = (g_rgb, g_depth, g_opacity, g_weights[, g_depth_var, g_rgb_var, g_all_cumulated, g_density, g_rgb_samples]), any may be
-    None; with `segs` a list of such tuples, one per ray segment (each tensor covering only its segment's rays).
-    prec with SAVE_MASKS (a ray-gradient-only pass): no parameter gradient is computed, the returned `gp` is None."""
-    lib = L.load()
+    """Allocate the results and fill the C struct of sparf_pass_backward (prepare_pass_bwd: `grads`, `segs`).  Returns
+    (struct, gp, dc, dd, keep): the parameter gradient [N_PARAMS] (None for a ray-gradient-only pass) and, with `pose`, the gradients
+    of the ray origins and directions."""
     dev = c.device
     R, N = tt.shape
-    ws = torch.empty(lib.sparf_bwd_workspace_bytes(prec, R, N, int(pose)), dtype=torch.uint8, device=dev)
-    gp = torch.empty(L.N_PARAMS, dtype=torch.float32, device=dev) if not (prec & L.SAVE_MASKS) else None
+    gp = torch.empty(L.N_PARAMS, dtype=torch.float32, device=dev) if has_param_grad(prec) else None
     dc = torch.empty(R, 3, dtype=torch.float32, device=dev) if pose else None
     dd = torch.empty(R, 3, dtype=torch.float32, device=dev) if pose else None
-    gseg = [[_f32(g) if g is not None else None for g in gt] for gt in grads] if segs else None
-    gs = [_f32(g) if g is not None else None for g in grads] if not segs else []       # (segmented: the table carries them)
-    gs += [None] * (9 - len(gs))
-    tables = L.tables_device(L.base_prec(prec), dev)
-    P = lambda x: x.data_ptr() if x is not None else None
-    a = _fill_pass_bwd(prec=prec, nrays=R, nsamp=N, center=P(c), dir=P(d), t=P(tt), noise=P(nz), noise_scale=noise_scale, white_bg=white_bg,
-                       packed=P(packed), c2f=P(c2f), tables=P(tables), save=P(save), raylen=P(fwd_out["raylen"]),
-                       sigma_raw=P(fwd_out["sigma_raw"]), rgb_samples=P(fwd_out["rgb_samples"]), weights=P(fwd_out["weights"]), ws=P(ws),
-                       grad_params=P(gp), d_center=P(dc), d_dir=P(dd), **{k: P(g) for k, g in zip(_GRAD_FIELDS, gs)})
-    keep = [ws, tables] + gs
-    if segs:
-        sa = _segments(segs, gseg)
-        a.nseg, a.seg = len(segs), sa
-        keep += [sa, gseg]
+    a, keep = prepare_pass_bwd(prec, R, N, dev, grads=grads, grad_params=_addr(gp), d_center=_addr(dc), d_dir=_addr(dd), noise_scale=noise_scale,
+                               white_bg=white_bg, segs=segs, center=_addr(c), dir=_addr(d), t=_addr(tt), noise=_addr(nz), packed=_addr(packed),
+                               c2f=_addr(c2f), save=_addr(save), **{k: _addr(fwd_out[k]) for k in ("raylen", "sigma_raw", "rgb_samples", "weights")})
     return a, gp, dc, dd, keep
 
 
@@ -302,9 +336,8 @@ class NerfPass(torch.autograd.Function):
         # needs_input_grad ignores the caller's grad mode (and forward() itself always runs with
         # grad disabled): `grad_mode` = torch.is_grad_enabled() at the call site.  Without it
         # nothing is saved and the inference kernel runs.
-        kind = save_kind(bool(grad_mode), ctx.needs_input_grad[0] or ctx.needs_input_grad[1], any(ctx.needs_input_grad[12:]), prec)
-        if kind == SAVE_NONE and bool(grad_mode) and any(ctx.needs_input_grad):
-            kind = SAVE_FULL                      # (some other input carries a gradient flag: as before)
+        kind = pass_save_kind(bool(grad_mode), ctx.needs_input_grad[0] or ctx.needs_input_grad[1], any(ctx.needs_input_grad[12:]), prec,
+                              any(ctx.needs_input_grad))
         need_grad = kind != SAVE_NONE
         prec = pass_prec_of(prec, kind)
         ctx.set_materialize_grads(False)          # absent upstream gradients arrive as None, not as zero tensors
@@ -636,8 +669,10 @@ def _plan(R, Nc, Nf):
     return p
 
 
-def _contig32(g):
-    return g if (g.dtype is torch.float32 and g.is_contiguous()) else g.detach().to(torch.float32).contiguous()
+# One pass of a render, as RenderFn's forward and backward see it.  tag: "c" | "f", the prefix of its results in the arena plan; prec: the
+# pass precision id (pass_prec_of).  The forward adds far ((K, far_prec) | None), the far_prec packed weights and the network's progress
+# scalar; the backward the address of the band weights its forward was given, its save area and the pass's nine upstream gradients.
+_Pass = namedtuple("_Pass", "tag N prec packed noise far far_packed prog c2f save grads", defaults=(None,) * 6)
 
 
 class RenderFn(torch.autograd.Function):
@@ -663,50 +698,47 @@ class RenderFn(torch.autograd.Function):
         need_grad = bool(cfg["grad"]) and any(ctx.needs_input_grad)
         # per pass: a network none of whose parameters wants a gradient (theta is None) under rays that do = a ray-gradient-only pass
         rays_grad = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
-        kinds = [save_kind(need_grad, rays_grad, ctx.needs_input_grad[14], cfg["prec_c"]), save_kind(need_grad, rays_grad, ctx.needs_input_grad[15], cfg["prec_f"])]
-        kinds = [SAVE_FULL if (need_grad and k == SAVE_NONE) else k for k in kinds]       # (a pass without differentiable inputs next to one with: as before)
+        precs = [pass_prec_of(cfg[k], pass_save_kind(bool(cfg["grad"]), rays_grad, ctx.needs_input_grad[i], cfg[k], need_grad))
+                 for k, i in (("prec_c", 14), ("prec_f", 15))]
         ctx.set_materialize_grads(False)
         arenas = (torch.empty(plan.total[0], dtype=torch.float32, device=dev), torch.empty(plan.total[1], dtype=torch.float32, device=dev))
         bases = (arenas[0].data_ptr(), arenas[1].data_ptr())
         A = lambda name: bases[plan.off[name][2]] + 4 * plan.off[name][0]
         stream = L.stream_ptr(dev)
-        precs = [pass_prec_of(cfg["prec_c"], kinds[0]), pass_prec_of(cfg["prec_f"], kinds[1])]
-        passes = [("c", Nc, precs[0], cfg["far_c"], packed_c, far_packed_c, noise_c, prog_c)]
+        passes = [_Pass("c", Nc, precs[0], packed_c, noise_c, cfg["far_c"], far_packed_c, prog_c)]
         if fine:
-            passes.append(("f", Nc + Nf, precs[1], cfg["far_f"], packed_f, far_packed_f, noise_f, prog_f))
+            passes.append(_Pass("f", Nc + Nf, precs[1], packed_f, noise_f, cfg["far_f"], far_packed_f, prog_f))
         saves, keep = [], []
         c2f_off = None if cfg["c2f"] is not None else c2f_weights(None, None, dev).data_ptr()     # no masking: the constant vector of the device
         with L.on(dev):
             L.check(lib.sparf_sample_coarse(L.ptr(jitter), float(cfg["u_const"]), None, L.ptr(range_dev), float(cfg["dmin"]), float(cfg["scale"]),
                                             int(cfg["inverse"]), R, Nc, c_void_p(A("ct")), stream), "sparf_sample_coarse")
-            for tag, N, prec, far, packed, far_packed, noise, prog in passes:
+            for p in passes:
+                tag = p.tag
                 if c2f_off is None:       # the pass's band weights, from the device value of its network's progress right now
-                    if prog.dtype is not torch.float32 or prog.device != dev:
+                    if p.prog.dtype is not torch.float32 or p.prog.device != dev:
                         raise L.SparfError("NeRF.progress must be a float32 scalar on the renderer's device")
-                    L.check(lib.sparf_c2f_weights(c_void_p(prog.data_ptr()), 1, float(cfg["c2f"][0]), float(cfg["c2f"][1]), c_void_p(A(tag + "c2f")), stream),
+                    L.check(lib.sparf_c2f_weights(c_void_p(p.prog.data_ptr()), 1, float(cfg["c2f"][0]), float(cfg["c2f"][1]), c_void_p(A(tag + "c2f")), stream),
                             "sparf_c2f_weights")
-                c2f_ptr = c2f_off if c2f_off is not None else A(tag + "c2f")
                 if tag == "f":
                     fn, grid = _fine_grid(lib, u_mid, dev)
                     L.check(fn(c_void_p(A("cweights")), c_void_p(A("ct")), L.ptr(grid), L.ptr(range_dev), float(cfg["dmin"]), float(cfg["dmax"]),
                                R, Nc, Nf, None, c_void_p(A("ft")), stream), "sparf_sample_fine")
-                save = torch.empty(lib.sparf_save_bytes(prec, R * N), dtype=torch.uint8, device=dev) if need_grad else None
-                venc = torch.empty(_venc_bytes(prec, R), dtype=torch.uint8, device=dev)
-                keep.append(venc)
-                a = _fill_pass_fwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=A(tag + "t"),
-                                   noise=noise.data_ptr() if noise is not None else None, noise_scale=cfg["noise_scale"] if noise is not None else 0.0,
-                                   white_bg=cfg["white_bg"], packed=packed.data_ptr(), c2f=c2f_ptr, save=save.data_ptr() if save is not None else None,
-                                   venc_ws=venc.data_ptr(), **{k: A(tag + k) for k, _, _ in _PASS_F32[:-1]})        # (all but "t": what the pass writes)
-                if far is not None:
-                    keep += _set_far(a, (far[0], far[1], far_packed), need_grad, prec, R, N, dev)
+                a, save, scratch = prepare_pass_fwd(
+                    p.prec, R, p.N, dev, save=need_grad, noise_scale=cfg["noise_scale"] if p.noise is not None else 0.0, white_bg=cfg["white_bg"],
+                    far=(p.far[0], p.far[1], p.far_packed.data_ptr()) if p.far is not None else None, center=c.data_ptr(), dir=d.data_ptr(),
+                    t=A(tag + "t"), noise=_addr(p.noise), packed=p.packed.data_ptr(), c2f=c2f_off if c2f_off is not None else A(tag + "c2f"),
+                    **{k: A(tag + k) for k, _, _ in _PASS_F32[:-1]})        # (all but "t": what the pass writes)
                 L.check(lib.sparf_pass_forward(ctypes.byref(a), stream), "sparf_pass_forward")
                 saves.append(save)
+                keep += scratch
         # the results: views of the two arenas, one split per arena + one view each
         pieces = {}
         for k in (0, 1):
             pieces.update(zip([n for n, _ in plan.order[k]], arenas[k].split_with_sizes([s for _, s in plan.order[k]])))
         outs = []
-        for tag, N, *_ in passes:
+        for p in passes:
+            tag, N = p.tag, p.N
             g = lambda name, *shape: pieces[tag + name][:plan.off[tag + name][1]].view(*shape) if plan.off[tag + name][1] != pieces[tag + name].numel() \
                 else pieces[tag + name].view(*shape)
             outs += [g("rgb", R, 3), g("depth", R), g("opacity", R), g("weights", R, N), g("depth_var", R), g("rgb_var", R), g("all_cumulated", R),
@@ -728,35 +760,27 @@ class RenderFn(torch.autograd.Function):
         A = lambda name: bases[plan.off[name][2]] + 4 * plan.off[name][0]
         pose = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         c2f_of = lambda tag: ctx.c2f_off if ctx.c2f_off is not None else A(tag + "c2f")       # the vector the forward of that pass was given
-        passes = [("c", Nc, ctx.precs[0], packed_c, noise_c, c2f_of("c"), saves[0], g[0:9])]
+        passes = [_Pass("c", Nc, ctx.precs[0], packed_c, noise_c, c2f=c2f_of("c"), save=saves[0], grads=g[0:9])]
         if npass == 2:
-            passes.append(("f", Nc + Nf, ctx.precs[1], packed_f, noise_f, c2f_of("f"), saves[1], g[10:19]))
-        active = [p for p in passes if any(x is not None for x in p[7])]
-        full = {p[0] for p in active if not (p[2] & L.SAVE_MASKS)}          # the passes that compute a parameter gradient
+            passes.append(_Pass("f", Nc + Nf, ctx.precs[1], packed_f, noise_f, c2f=c2f_of("f"), save=saves[1], grads=g[10:19]))
+        active = [p for p in passes if any(x is not None for x in p.grads)]
+        full = {p.tag for p in active if has_param_grad(p.prec)}
         gp = torch.empty(2, L.N_PARAMS, dtype=torch.float32, device=dev) if full else None
-        rays = torch.empty(2, R, 3, dtype=torch.float32, device=dev) if pose else None
+        rays = torch.empty(2, R, 3, dtype=torch.float32, device=dev) if (pose and active) else None
         stream = L.stream_ptr(dev)
         keep = []
         with L.on(dev):
-            first = True
-            for tag, N, prec, packed, noise, c2f, save, gs in active:
-                gs = [(_contig32(x) if x is not None else None) for x in gs]
-                ws = torch.empty(lib.sparf_bwd_workspace_bytes(prec, R, N, int(pose)), dtype=torch.uint8, device=dev)
-                tables = L.tables_device(L.base_prec(prec), dev)
-                P = lambda x: x.data_ptr() if x is not None else None
-                a = _fill_pass_bwd(prec=prec, nrays=R, nsamp=N, center=c.data_ptr(), dir=d.data_ptr(), t=A(tag + "t"), noise=P(noise),
-                                   noise_scale=cfg["noise_scale"] if noise is not None else 0.0, white_bg=cfg["white_bg"], packed=packed.data_ptr(),
-                                   c2f=c2f, tables=tables.data_ptr(), save=save.data_ptr(), raylen=A(tag + "raylen"), sigma_raw=A(tag + "sigma_raw"),
-                                   rgb_samples=A(tag + "rgb_samples"), weights=A(tag + "weights"), ws=ws.data_ptr(),
-                                   grad_params=gp.data_ptr() + (0 if tag == "c" else 4 * L.N_PARAMS) if tag in full else None, d_center=P(rays[0]) if pose else None,
-                                   d_dir=P(rays[1]) if pose else None, accumulate_rays=0 if first else 1, **{k: P(x) for k, x in zip(_GRAD_FIELDS, gs)})
+            for i, p in enumerate(active):
+                a, scratch = prepare_pass_bwd(
+                    p.prec, R, p.N, dev, grads=p.grads, grad_params=gp.data_ptr() + (0 if p.tag == "c" else 4 * L.N_PARAMS) if p.tag in full else None,
+                    d_center=_addr(rays[0]) if pose else None, d_dir=_addr(rays[1]) if pose else None, accumulate_rays=int(i > 0),
+                    noise_scale=cfg["noise_scale"] if p.noise is not None else 0.0, white_bg=cfg["white_bg"], center=c.data_ptr(), dir=d.data_ptr(),
+                    t=A(p.tag + "t"), noise=_addr(p.noise), packed=p.packed.data_ptr(), c2f=p.c2f, save=p.save.data_ptr(),
+                    **{k: A(p.tag + k) for k in ("raylen", "sigma_raw", "rgb_samples", "weights")})
                 L.check(lib.sparf_pass_backward(ctypes.byref(a), stream), "sparf_pass_backward")
-                keep += [ws, gs]
-                first = False
+                keep += scratch
         g_c = gp[0] if "c" in full else None
-        g_f = gp[1] if ("f" in full and npass == 2) else None
-        if not active:
-            rays = None
+        g_f = gp[1] if "f" in full else None
         return (rays[0] if (rays is not None and ctx.needs_input_grad[0]) else None, rays[1] if (rays is not None and ctx.needs_input_grad[1]) else None,
                 None, None, None, None, None, None, None, None, None, None, None, None, g_c, g_f)
 

@@ -16,9 +16,9 @@ from . import camera
 from . import lib as L
 from . import ops
 from .batch_plan import Member, plan
-from .config import hip_option
+from .config import hip_env, hip_option
 from .edict import EasyDict as edict, opt_get
-from .frequency_nerf import FrequencyEmbedder, NeRF, max_rows_per_call, pass_precision, shape_pass
+from .frequency_nerf import FrequencyEmbedder, NeRF, density_noise_on, max_rows_per_call, pass_precision, precision_name, shape_pass, white_bg
 
 
 _LOGGED_MODES = set()
@@ -29,9 +29,15 @@ def _as_float(x):
 
 
 def _nets_frozen(opt, mode):
-    """opt.hip.test_optim_rays_only (config.HIP_DEFAULTS: off): a render of the test-time pose optimisation hands the networks' parameters to no
+    """opt.hip.test_optim_rays_only (config.HIP_KEYS: off): a render of the test-time pose optimisation hands the networks' parameters to no
     autograd node -- their .grad stay untouched, the passes run ray-gradient-only"""
     return mode == "test-optim" and bool(hip_option(opt, "test_optim_rays_only"))
+
+
+def _rays_fused(opt, *inputs):
+    """whether ray generation is the fused launch (ops.RayGen / RayGenMany, with backward to the pose) for a request: `opt.hip.fused_rays`
+    (default on), and none of `inputs` -- its intrinsics; its pixel lists where the launch sees them as plain data -- needs a gradient"""
+    return bool(hip_option(opt, "fused_rays")) and not any(x is not None and x.requires_grad for x in inputs)
 
 
 def _deterministic(opt, mode):
@@ -202,12 +208,10 @@ class Graph(torch.nn.Module):
         self.device = device
         self._pinned, self._pinned_i = {}, 0
         self._pending, self.lazy_stats = None, dict(batches=0, requests=0)          # lazy batching of back-to-back render calls (PendingRender)
-        import os
-        self._lazy_env = os.environ.get("SPARF_LAZY_BATCH")                          # "0" / "1" overrides opt.hip.lazy_batch (A/B runs of an unmodified trainer)
+        self._env = hip_env("lazy_batch")        # $SPARF_LAZY_BATCH as it is NOW: "0" / "1" overrides opt.hip.lazy_batch (A/B runs of an unmodified trainer)
         _register_graph(self)
         self.define_renderer(opt)
         # which arithmetic an unmodified trainer got: once per process and mode, at INFO level
-        from .frequency_nerf import precision_name
         name = precision_name(opt)
         if name not in _LOGGED_MODES:
             _LOGGED_MODES.add(name)
@@ -305,11 +309,9 @@ class Graph(torch.nn.Module):
         """Ray origins / directions of the selected pixels (renderer.py:273-291).  One fused
         launch (ops.RayGen, with backward to the pose) unless the intrinsics need a gradient or
         `opt.hip.fused_rays` is False, in which case the PyTorch restatement in camera.py runs."""
-        hip = opt_get(opt, "hip")
-        fused = (hip is None or hip.get("fused_rays", True)) and not intr.requires_grad
         if ray_idx is not None:
             ray_idx = ops.ray_request(len(pose), None, ray_idx)[2]
-        if fused:
+        if _rays_fused(opt, intr):
             if pixels is None and ray_idx is None:
                 ray_idx = torch.arange(H * W, device=pose.device)
             center, ray = ops.ray_gen(pose, intr, pixels=pixels, ray_idx=None if pixels is not None else ray_idx, width=W)
@@ -382,10 +384,8 @@ class Graph(torch.nn.Module):
         (`_draw_randoms`): the RNG streams -- and a test harness that injects draws around the call -- see exactly the eager sequence; only
         the kernel launches wait.  A batch is launched by the first read of any of its results, by the next call into the renderer
         that is not deferred, or by the next optimiser step."""
-        hip = opt_get(opt, "hip")
-        lazy = (hip is None or hip.get("lazy_batch", True)) if self._lazy_env is None else self._lazy_env != "0"
-        if not lazy or (hip is not None and not hip.get("fused_rays", True)) \
-                or mode != "train" or not torch.is_grad_enabled() or opt.camera.ndc or intr.requires_grad:
+        if not hip_option(opt, "lazy_batch", env=self._env) or not _rays_fused(opt, intr) \
+                or mode != "train" or not torch.is_grad_enabled() or opt.camera.ndc:
             return None
         L.require_gpu(pose.device)
         B = pose.shape[0]
@@ -404,8 +404,7 @@ class Graph(torch.nn.Module):
     def _fused_route(self, opt, n, iter, device):
         """-> (fine, prec, far) of a render of n rays that takes the fused one-node route (_render_fused), or None where it does not:
         `opt.hip.fused_render` off, no rays, or more sample rows in its passes than one launch set takes"""
-        hip = opt_get(opt, "hip")
-        if n == 0 or (hip is not None and not hip.get("fused_render", True)):
+        if n == 0 or not hip_option(opt, "fused_render"):
             return None
         fine = self._fine_on(opt, iter)
         prec, far = pass_precision(opt, int(opt.nerf.sample_intvs))
@@ -423,11 +422,11 @@ class Graph(torch.nn.Module):
             jitter = torch.rand(B, R, Nc, 1, device=self.device)
             if jitter.dtype is not torch.float32 or not jitter.is_contiguous():
                 jitter = jitter.float().contiguous()
-        use_noise = bool(opt.nerf.density_noise_reg) and mode == "train"
+        use_noise = density_noise_on(opt, mode)
         noise_c = torch.randn(n, Nc, device=dev) if use_noise else None                 # frequency_nerf.py:192
         u_mid = noise_f = None
         if fine:
-            u_mid = self._grid_midpoints_fused(Nf, _deterministic(opt, mode))
+            u_mid = self._grid_midpoints(Nf, _deterministic(opt, mode), host_ok=True)
             noise_f = torch.randn(n, Nc + Nf, device=dev) if use_noise else None
         for z in (noise_c, noise_f):
             if z is not None and (z.dtype is not torch.float32 or not z.is_contiguous()):
@@ -519,7 +518,7 @@ class Graph(torch.nn.Module):
         theta_f = self.nerf_fine.flat_params(pf) if (grad and fine) else None
         fprec = far[1] if far is not None else None
         cfg = dict(R=n, Nc=Nc, Nf=Nf, fine=fine, dmin=dmin, dmax=dmax, scale=scale, inverse=opt.nerf.depth.param == "inverse", u_const=0.5,
-                   noise_scale=float(opt.nerf.density_noise_reg) if use_noise else 0.0, white_bg=bool(opt.nerf.setbg_opaque or opt.mask_img),
+                   noise_scale=float(opt.nerf.density_noise_reg) if use_noise else 0.0, white_bg=white_bg(opt),
                    prec_c=prec, prec_f=prec, far_c=far, far_f=far, c2f=tuple(float(x) for x in opt.barf_c2f) if opt.barf_c2f is not None else None)
         coarse, fine_out = ops.render_fused(
             center.reshape(n, 3), ray.reshape(n, 3), cfg, jitter.view(n, Nc) if jitter is not None else None, u_mid, noise_c, noise_f, rd,
@@ -594,20 +593,10 @@ class Graph(torch.nn.Module):
                               jitter=jitter, u_const=0.5, range_dev=rd, out=out)
         return t.view(batch_size, num_rays, n_samples, 1)
 
-    def _grid_midpoints_fused(self, n_fine, det):
-        """the mid-points for the fused render: a HOST float32 tensor where the grid is drawn on the CPU as the reference does
-        (renderer.py:439) and fits the launch arguments (C ABI sparf_sample_fine_hostgrid: no host -> device copy at all), else the
-        device tensor of _grid_midpoints"""
-        hip = opt_get(self.opt, "hip")
-        if det or n_fine > 256 or (hip is not None and hip.get("device_rng", False)):
-            return self._grid_midpoints(n_fine, det)
-        cpu = torch.rand(n_fine + 1)
-        if cpu.device.type != "cpu" or cpu.dtype is not torch.float32:
-            return 0.5 * (cpu[:-1] + cpu[1:]).to(device=self.device, dtype=torch.float32)
-        return (0.5 * (cpu[:-1] + cpu[1:])).contiguous()       # the same two fp32 operations the reference runs on the device: same bits
-
-    def _grid_midpoints(self, n_fine, det):
-        """mid-points u_j = (g_j + g_{j+1}) / 2 of the fine-sampling grid (renderer.py:434-441), [n_fine] on the device"""
+    def _grid_midpoints(self, n_fine, det, host_ok=False):
+        """mid-points u_j = (g_j + g_{j+1}) / 2 of the fine-sampling grid (renderer.py:434-441), [n_fine] on the device -- or, with
+        host_ok (the fused render), a HOST float32 tensor where the grid is drawn on the CPU as the reference does (renderer.py:439) and
+        fits the launch arguments (C ABI sparf_sample_fine_hostgrid: no host -> device copy at all)"""
         if det:
             key = ("det", n_fine)
             mid = self._pinned.get(key)
@@ -615,20 +604,24 @@ class Graph(torch.nn.Module):
                 grid = torch.linspace(0, 1, n_fine + 1, device=self.device)
                 mid = self._pinned[key] = 0.5 * (grid[:-1] + grid[1:])
             return mid
-        # one shared, unsorted draw made on the CPU, as the reference does (renderer.py:439),
-        # but staged through a small ring of pinned buffers: a pageable .to(device) would
-        # block the host behind everything already queued on the stream, every step
-        hip = opt_get(self.opt, "hip")
-        if hip is not None and hip.get("device_rng", False):
+        if hip_option(self.opt, "device_rng"):
             # opt.hip.device_rng: draw on the device instead (same distribution, different
             # RNG stream) -- keeps the whole step free of host->device copies, which is
             # what hipGraph capture of a training step needs
             grid = torch.rand(n_fine + 1, device=self.device)
             return 0.5 * (grid[:-1] + grid[1:])
+        # one shared, unsorted draw made on the CPU, as the reference does (renderer.py:439)
         cpu = torch.rand(n_fine + 1)
-        if cpu.device.type != "cpu":         # (a test harness replaying recorded draws may hand back a device tensor)
-            return 0.5 * (cpu[:-1] + cpu[1:]).to(self.device)
+        host = host_ok and n_fine <= 256
+        if cpu.device.type != "cpu" or (host and cpu.dtype is not torch.float32):
+            # (a test harness replaying recorded draws may hand back a device tensor, or another type)
+            both = cpu[:-1] + cpu[1:]
+            return 0.5 * (both.to(device=self.device, dtype=torch.float32) if host else both.to(self.device))
         mid = 0.5 * (cpu[:-1] + cpu[1:])     # the same two fp32 operations the reference runs on the device: same bits
+        if host:
+            return mid.contiguous()
+        # staged through a small ring of pinned buffers: a pageable .to(device) would
+        # block the host behind everything already queued on the stream, every step
         if torch.device(self.device).type == "cuda":
             ring = self._pinned.setdefault(n_fine, [[torch.empty(n_fine).pin_memory(), None] for _ in range(8)])
             self._pinned_i = (self._pinned_i + 1) % len(ring)
@@ -710,7 +703,6 @@ class Graph(torch.nn.Module):
         if opt.camera.ndc:
             raise NotImplementedError("camera.ndc is dead code in the reference (renderer.py:295 vs camera.py:439) and unsupported here")
         Nc, Nf, dev = opt.nerf.sample_intvs, opt.nerf.sample_intvs_fine, self.device
-        white_bg = bool(opt.nerf.setbg_opaque or opt.mask_img)
         members = []
         for q in requests:
             B = q["pose"].shape[0]
@@ -728,12 +720,9 @@ class Graph(torch.nn.Module):
         for blk in blocks:
             with torch.set_grad_enabled(not blk.nograd):
                 # ray generation of the whole block into one (centres, directions) buffer, each request at its offset
-                hip = opt_get(opt, "hip")
                 # (pixel lists that carry a gradient -- depth_cons_loss.py:291 -- take the per-request path: ops.RayGenMany sees its
                 # pixel lists as plain data)
-                fused = (hip is None or hip.get("fused_rays", True)) and not any(
-                    m.q["intr"].requires_grad or (m.q.get("pixels") is not None and m.q["pixels"].requires_grad) for m in blk.members)
-                if fused:
+                if _rays_fused(opt, *[x for m in blk.members for x in (m.q["intr"], m.q.get("pixels"))]):
                     specs = []
                     for m in blk.members:
                         px, ix = m.q.get("pixels"), m.q.get("ray_idx")
@@ -755,7 +744,7 @@ class Graph(torch.nn.Module):
                         self._sample_depth(opt, m.B, num_rays=m.R, n_samples=Nc, H=q["H"], W=q["W"], depth_range=q["depth_range"],
                                            mode=m.mode, out=t_all[rows], jitter=m.draws.get("jitter"))
                 for p in blk.coarse:
-                    self._batch_pass(p, rays, t_all, white_bg, opt)
+                    self._batch_pass(p, rays, t_all, opt)
                 # render requests: resample + merge per request (own depth range / grid), into one [R, Nc+Nf] buffer; the fine network
                 # sees render_to_max requests on the SAME samples as the coarse one (renderer.py:583-592)
                 t_fine = torch.empty(blk.merged_rows, Nc + Nf, device=dev, dtype=torch.float32) if blk.merged_rows is not None else None
@@ -767,10 +756,10 @@ class Graph(torch.nn.Module):
                                         u_mid if u_mid is not None else self._grid_midpoints(Nf, _deterministic(opt, m.mode)), dmin, dmax,
                                         range_dev=rd, out=t_fine[m.off:m.off + m.n])
                 for p in blk.fine:
-                    self._batch_pass(p, rays, t_fine if p.merged else t_all, white_bg, opt)
+                    self._batch_pass(p, rays, t_fine if p.merged else t_all, opt)
         return [m.pred for m in members]
 
-    def _batch_pass(self, p, rays, t_buf, white_bg, opt=None):
+    def _batch_pass(self, p, rays, t_buf, opt):
         """issue one planned pass (batch_plan.Pass) of a render_batch block: `rays`, `t_buf` are the block's ray and depth buffers"""
         net = self.nerf_fine if p.fine else self.nerf
         far = (p.far[0], p.far[1], net.packed(p.far[1])) if p.far is not None else None
@@ -782,9 +771,9 @@ class Graph(torch.nn.Module):
             else:
                 noise = torch.randn(p.hi - p.lo, p.N, device=self.device)
         params = net.hip_params()
-        if p.members and all(_nets_frozen(opt if opt is not None else self.opt, m.mode) for m in p.members):          # (what routes the parameter gradient: nothing)
+        if p.members and all(_nets_frozen(opt, m.mode) for m in p.members):          # (what routes the parameter gradient: nothing)
             params = [x.detach() for x in params]
-        outs = ops.nerf_pass_segments(rays[0, p.lo:p.hi], rays[1, p.lo:p.hi], t_buf[p.lo:p.hi], noise, white_bg, p.prec, net.packed(p.prec),
+        outs = ops.nerf_pass_segments(rays[0, p.lo:p.hi], rays[1, p.lo:p.hi], t_buf[p.lo:p.hi], noise, white_bg(opt), p.prec, net.packed(p.prec),
                                       net.band_weights(), params, p.segs, far=far)
         suffix = p.suffix
         for m, o in zip(p.members, outs):

@@ -2,7 +2,7 @@
 of the masks-only save area and of the backward workspace, the routing function of the Python glue, the compiled instruction
 stream of the seven new kernels against their plane-saving counterparts (tools/kernel_stream.py; a unit without a current object is
 compiled first), and the route as the C ABI sees it -- ops.NerfPass, ops.RenderFn, Graph.render and Graph.render_batch on CPU tensors
-over a stand-in library that launches nothing and records the precision id and grad_params of every pass call."""
+over a stand-in library (tests/glue_fake.py) that launches nothing and records the precision id and grad_params of every pass call."""
 import importlib.util
 import os
 import re
@@ -11,6 +11,7 @@ import pytest
 
 from sparf_amd import lib as L
 from sparf_amd import ops
+from tests.glue_fake import fake  # noqa: F401  (the stand-in library, as a fixture)
 from tests.test_kernel_stream_cpu import _BWD, _BWX, _FWD, ALL_KERNELS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -134,42 +135,6 @@ def test_compiled_stream_against_the_plane_saving_counterpart(stream, unit):
 
 
 # ---------------------------------------------------------------------------------------------- the route as the C ABI sees it, no GPU
-class _FakeLib:
-    """stands in for the loaded library under ops.NerfPass / ops.RenderFn: launches nothing, sizes areas with the real library's host
-    arithmetic, records (prec, grad_params) of every pass call"""
-
-    def __init__(self):
-        self.real = L.load()
-        self.fwd, self.bwd = [], []
-
-    def __getattr__(self, name):
-        if name in ("sparf_save_bytes", "sparf_bwd_workspace_bytes"):
-            return getattr(self.real, name)
-        return lambda *a: 0
-
-    def sparf_pass_forward(self, a, stream):
-        self.fwd.append((a._obj.prec, a._obj.nsamp, a._obj.save is not None))
-        return 0
-
-    def sparf_pass_backward(self, a, stream):
-        assert self.real.sparf_bwd_workspace_bytes(a._obj.prec, a._obj.nrays, a._obj.nsamp, 1) > 0
-        self.bwd.append((a._obj.prec, a._obj.nsamp, a._obj.grad_params is not None))
-        return 0
-
-
-@pytest.fixture
-def fake(monkeypatch):
-    import contextlib
-    import torch
-    lib = _FakeLib()
-    monkeypatch.setattr(L, "load", lambda: lib)
-    monkeypatch.setattr(L, "require_gpu", lambda d: d)
-    monkeypatch.setattr(L, "on", lambda d: contextlib.nullcontext())
-    monkeypatch.setattr(L, "stream_ptr", lambda d: None)
-    monkeypatch.setattr(L, "tables_device", lambda prec, d: torch.zeros(4, dtype=torch.int32))
-    return lib
-
-
 def _params(requires_grad):
     import torch
     return [torch.zeros(n, requires_grad=requires_grad) for (o, i) in L.LAYER_SHAPES for n in ((o, i), (o,))]
