@@ -10,10 +10,13 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsparf_hip.so")
-# (the slow units first: they are compiled in parallel and set the build's wall time)
-SOURCES = ["mlp_fwd_fp32_train.hip", "mlp_fwd_fp32_infer.hip", "rays_fwd_fp32.hip", "rays_bwd_fp32.hip", "mlp_fwd_x3_train.hip", "rays_fwd_x3.hip", "mlp_fwd_x3_train_q8.hip", "mlp_fwd_x3_infer.hip", "mlp_bwd.hip", "mlp_bwd_fp32.hip", "mlp_bwd_x3.hip", "mlp_bwd_x3w4.hip", "mlp_bwd_q8.hip", "rays_bwd_x3.hip", "rays_bwd_x3w4.hip", "rays_bwd.hip", "rays_fwd_bf16.hip",
-           "mlp_fwd_bf16_train.hip", "mlp_fwd_bf16_train_q8.hip", "mlp_fwd_bf16_infer.hip", "wgrad.hip", "api.hip", "mlp_fwd.hip", "ray_ops.hip", "pack.hip", "optim.hip", "calib.hip",
-           "tables.cpp"]
+# The fused MLP kernel units: each is the explicit instantiations of the kernels of csrc/kernels.h' lists that it holds and nothing else
+# (the slow units first: they are compiled in parallel and set the build's wall time).  RAYS_UNITS: those of ray-gradient-only passes.
+FUSED_UNITS = ["mlp_fwd_fp32_train.hip", "mlp_fwd_fp32_infer.hip", "rays_fwd_fp32.hip", "rays_bwd_fp32.hip", "mlp_fwd_x3_train.hip", "rays_fwd_x3.hip", "mlp_fwd_x3_train_q8.hip", "mlp_fwd_x3_infer.hip", "mlp_bwd.hip", "mlp_bwd_fp32.hip", "mlp_bwd_x3.hip", "mlp_bwd_x3w4.hip", "mlp_bwd_q8.hip", "rays_bwd_x3.hip", "rays_bwd_x3w4.hip", "rays_bwd.hip", "rays_fwd_bf16.hip",
+               "mlp_fwd_bf16_train.hip", "mlp_fwd_bf16_train_q8.hip", "mlp_fwd_bf16_infer.hip"]
+RAYS_UNITS = ["rays_fwd_fp32.hip", "rays_bwd_fp32.hip", "rays_fwd_x3.hip", "rays_bwd_x3.hip", "rays_bwd_x3w4.hip", "rays_bwd.hip", "rays_fwd_bf16.hip"]
+MLP_DISPATCH = "mlp_launch.hip"      # their dispatch: host code only
+SOURCES = FUSED_UNITS + ["wgrad.hip", "api.hip", MLP_DISPATCH, "ray_ops.hip", "pack.hip", "optim.hip", "calib.hip", "tables.cpp"]
 HEADERS = ["layout.h", "streams.h", "mlp_dev.h", "mlp_fwd_impl.h", "mlp_bwd_impl.h", "kernels.h", "pass_plan.h", os.path.join("..", "..", "include", "sparf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-fconstexpr-steps=200000000"]
 
@@ -78,7 +81,8 @@ def build(force=False, verbose=True, out=None, extra_flags=(), tag="", only=None
     if failed:
         raise RuntimeError("hipcc failed:\n" + "\n".join(f"--- {s}\n{o}" for s, o in failed))
     if force or procs or _newer(out, objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs
+        # (--no-undefined: a kernel that csrc/kernels.h lists and no unit instantiates fails here, not when the library is loaded)
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", out] + objs
         if verbose:
             print("[sparf_amd.build]", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)

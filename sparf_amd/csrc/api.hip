@@ -31,27 +31,12 @@ static int zero_rays(float* d_center, float* d_dir, int first, int last, hipStre
     return hipMemsetAsync(d_center + off, 0, bytes, s) == hipSuccess && hipMemsetAsync(d_dir + off, 0, bytes, s) == hipSuccess ? 0 : 2;
 }
 static inline int launch_fwd(const FwdLaunch& l, hipStream_t s) { return launch_mlp_fwd(l.prec, l.save, l.a, mlp_grid(l.prec, l.a.rows), s); }
-// the data-gradient launch(es) of a plan over its active rows: [row0, row0 + rows8) in 8 waves, the rest, if any, in 4 (bf16x3 with plane
-// areas picks its geometry per range, pass_plan.h x3_dgrad_rows8); `pin` (measurement: sparf_launch_kernel 3 / 4) forces one geometry
-// of that kernel for the whole range
-static int launch_dgrad(const BwdPlan& b, hipStream_t s, int pin = 0) {
-    const int prec = b.pp.base;
-    const int64_t rows = b.row1 - b.row0;
-    const int64_t rows8 = prec != PREC_X3 || b.pp.q8 || pin == 8 ? rows : pin == 4 ? 0 : b.rows8;
-    // (a ray-gradient-only pass: the kernels without dY stores over the masks-only save area, same geometries)
-    auto launch = [&](const MlpBwdArgs& a, int64_t n, int waves) {
-        return b.pp.masks ? launch_mlp_bwd_rays(prec, a, mlp_grid(prec, n), s, waves) : launch_mlp_bwd(prec, b.pose, b.pp.q8, a, mlp_grid(prec, n), s, waves);
-    };
+// the data-gradient launch(es) of a plan, in its order
+static int launch_dgrad(const BwdPlan& b, hipStream_t s) {
     int rc = 0;
-    if (rows8 > 0) {
-        MlpBwdArgs a = b.m;
-        a.rows = b.row0 + rows8;
-        rc = launch(a, rows8, 8);
-    }
-    if (!rc && rows8 < rows) {
-        MlpBwdArgs a = b.m;
-        a.row_begin = b.row0 + rows8;
-        rc = launch(a, rows - rows8, 4);
+    for (int i = 0; !rc && i < b.ndgrad; ++i) {
+        const BwdLaunch& l = b.dgrad[i];
+        rc = launch_mlp_bwd(l.k->prec, l.k->pose, l.k->save, l.k->waves, l.a, mlp_grid(l.k->prec, l.n), s);
     }
     return rc;
 }
@@ -271,11 +256,11 @@ int sparf_launch_kernel(int which, const sparf_pass_fwd_t* f, const sparf_pass_b
     }
     if (which < 1 || which > 4) return 1;
     BwdPlan b;
-    const int rc = plan_backward(p, true, &b);
+    const int rc = plan_backward(p, true, &b, which == 3 ? 8 : which == 4 ? 4 : 0);      // 3 / 4: the bf16x3 kernel pinned to its 8-wave / 4-wave geometry
     if (rc || b.rows == 0) return rc;
     if (which == 2 && b.pp.masks) return 1;                              // a ray-gradient-only pass has no weight gradient
     if (which == 2) return launch_wgrad(b.pp.base, b.pp.q8, b.g, b.split.nsplit, p->tables + kWsrcOff[b.pp.base], p->grad_params, s);
-    return launch_dgrad(b, s, which == 1 ? 0 : which == 3 ? 8 : 4);      // 3 / 4: the bf16x3 kernel pinned to its 8-wave / 4-wave geometry
+    return launch_dgrad(b, s);
 }
 
 // ---- calibration (measurement only, sparf_hip.h): fixed kernels that do not change with the renderer's

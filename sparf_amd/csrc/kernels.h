@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "layout.h"
+
 namespace sparf {
 
 struct MlpFwdArgs {
@@ -39,7 +41,6 @@ static __host__ __device__ inline int64_t routed_row(int64_t r, int nsamp, int r
 // what the forward kernel leaves behind for the backward.  FWD_SAVE_MASKS: the ReLU mask words only, in an AREA_MASKS save area (layout.h):
 // all the data gradient of a ray-gradient-only pass reads
 enum { FWD_INFER = 0, FWD_SAVE_PLANES = 1, FWD_SAVE_Q8 = 2, FWD_SAVE_MASKS = 3 };
-int launch_mlp_fwd(int prec, int save, const MlpFwdArgs& a, int grid, hipStream_t stream);
 
 struct MlpBwdArgs {
     const char* packed;
@@ -56,11 +57,86 @@ struct MlpBwdArgs {
     int64_t row_begin;         // first active row (multiple of 32): rows before it belong to ray segments without upstream gradient
     int64_t rows_total;        // rows of the whole pass (= what the save / gradient areas were sized for)
 };
-// q8: the save / gradient areas are in the 8-bit format (layout.h AREA_Q8; bf16-operand modes)
-// waves: workgroup geometry of the bf16x3 kernel, 8 (256-row tiles, the default) or 4 (128-row tiles); other precisions have one geometry
-int launch_mlp_bwd(int prec, bool pose, bool q8, const MlpBwdArgs& a, int grid, hipStream_t stream, int waves = 8);
-// the data gradient of a ray-gradient-only pass (rays_bwd.hip): the pose variant over an AREA_MASKS save area, no dY stores (a.grad is not read)
-int launch_mlp_bwd_rays(int prec, const MlpBwdArgs& a, int grid, hipStream_t stream, int waves = 8);
+
+// ---- The fused MLP kernels: every instance of mlp_fwd_kernel / mlp_bwd_kernel the library holds is one line of the two lists below.
+// The launchers' explicit-instantiation declarations, the tables the dispatch (mlp_launch.hip) looks kernels up in and the rules the
+// plan of a pass goes by (pass_plan.h) are all made from these lines; the translation unit that holds a kernel is the one that
+// explicitly instantiates its launcher (defined by mlp_fwd_impl.h / mlp_bwd_impl.h), and a line without one does not link.
+//   forward  (precision, what it leaves behind: FWD_*)
+//   backward (precision, pose gradients, waves per workgroup, what its forward left: FWD_SAVE_*)
+#define SP_MLP_FWD_KERNELS(X) \
+    X(PREC_BF16, FWD_INFER) X(PREC_BF16, FWD_SAVE_PLANES) X(PREC_BF16, FWD_SAVE_Q8) X(PREC_BF16, FWD_SAVE_MASKS) \
+    X(PREC_FP32, FWD_INFER) X(PREC_FP32, FWD_SAVE_PLANES) X(PREC_FP32, FWD_SAVE_MASKS) \
+    X(PREC_X3, FWD_INFER) X(PREC_X3, FWD_SAVE_PLANES) X(PREC_X3, FWD_SAVE_Q8) X(PREC_X3, FWD_SAVE_MASKS)
+#define SP_MLP_BWD_KERNELS(X) \
+    X(PREC_BF16, false, 8, FWD_SAVE_PLANES) X(PREC_BF16, true, 8, FWD_SAVE_PLANES) \
+    X(PREC_BF16, false, 8, FWD_SAVE_Q8) X(PREC_BF16, true, 8, FWD_SAVE_Q8) X(PREC_BF16, true, 8, FWD_SAVE_MASKS) \
+    X(PREC_FP32, false, 4, FWD_SAVE_PLANES) X(PREC_FP32, true, 4, FWD_SAVE_PLANES) X(PREC_FP32, true, 4, FWD_SAVE_MASKS) \
+    X(PREC_X3, false, 8, FWD_SAVE_PLANES) X(PREC_X3, true, 8, FWD_SAVE_PLANES) X(PREC_X3, false, 4, FWD_SAVE_PLANES) X(PREC_X3, true, 4, FWD_SAVE_PLANES) \
+    X(PREC_X3, false, 8, FWD_SAVE_Q8) X(PREC_X3, true, 8, FWD_SAVE_Q8) X(PREC_X3, true, 8, FWD_SAVE_MASKS) X(PREC_X3, true, 4, FWD_SAVE_MASKS)
+
+// both return 0 without a launch when a.rows <= 0, else 2 if the launch failed
+template <int PREC, int SAVE> int launch_mlp_fwd_t(const MlpFwdArgs& a, int grid, hipStream_t stream);
+template <int PREC, bool POSE, int WAVES, int SAVE> int launch_mlp_bwd_t(const MlpBwdArgs& a, int grid, hipStream_t stream);
+// (declared extern: a unit that sees the launchers' definition instantiates the kernels it names itself and no others)
+#define SP_FWD_EXTERN(P, S) extern template int launch_mlp_fwd_t<P, S>(const MlpFwdArgs&, int, hipStream_t);
+#define SP_BWD_EXTERN(P, POSE, W, S) extern template int launch_mlp_bwd_t<P, POSE, W, S>(const MlpBwdArgs&, int, hipStream_t);
+SP_MLP_FWD_KERNELS(SP_FWD_EXTERN)
+SP_MLP_BWD_KERNELS(SP_BWD_EXTERN)
+#undef SP_FWD_EXTERN
+#undef SP_BWD_EXTERN
+
+struct MlpFwdKernel {
+    int prec, save;
+    int (*launch)(const MlpFwdArgs&, int, hipStream_t);
+};
+struct MlpBwdKernel {
+    int prec;
+    bool pose;
+    // Workgroup geometry: its tile is waves * 32 rows.  The bf16x3 kernel over plane or masks-only areas comes in two, 8 (256-row tiles,
+    // cheaper per row) and 4 (128-row tiles); pass_plan.h plan_dgrad picks per row range.  The GRID of a launch is sized by
+    // pass_plan.h mlp_grid(prec, rows), i.e. by the forward's tile of nwaves_of(prec) * 32 rows, not by this one: the 8-wave bf16x3
+    // launch gets twice the workgroups its 256-row tiles need when the rows are under one round (the surplus ones find no tile and
+    // leave).  As found; changing it is a change of performance that wants its own measurement.
+    int waves;
+    int save;
+    int (*launch)(const MlpBwdArgs&, int, hipStream_t);
+};
+#define SP_FWD_ROW(P, S) {P, S, &launch_mlp_fwd_t<P, S>},
+#define SP_BWD_ROW(P, POSE, W, S) {P, POSE, W, S, &launch_mlp_bwd_t<P, POSE, W, S>},
+static constexpr MlpFwdKernel kMlpFwd[] = {SP_MLP_FWD_KERNELS(SP_FWD_ROW)};
+static constexpr MlpBwdKernel kMlpBwd[] = {SP_MLP_BWD_KERNELS(SP_BWD_ROW)};
+#undef SP_FWD_ROW
+#undef SP_BWD_ROW
+// nullptr: no such kernel
+constexpr const MlpFwdKernel* find_mlp_fwd(int prec, int save) {
+    for (const MlpFwdKernel& k : kMlpFwd)
+        if (k.prec == prec && k.save == save) return &k;
+    return nullptr;
+}
+constexpr const MlpBwdKernel* find_mlp_bwd(int prec, bool pose, int waves, int save) {
+    for (const MlpBwdKernel& k : kMlpBwd)
+        if (k.prec == prec && k.pose == pose && k.waves == waves && k.save == save) return &k;
+    return nullptr;
+}
+// What the lists must satisfy among themselves for the plan to lean on them:
+//   * every data-gradient kernel has the forward that leaves what it reads;
+//   * plan_dgrad chooses the geometry from the row count alone, so a (precision, save kind) offers the same geometries with and
+//     without pose gradients, and a ray-gradient-only pass (masks: pose variant only) the ones of the pass over plane areas.
+constexpr bool mlp_tables_consistent() {
+    for (const MlpBwdKernel& k : kMlpBwd) {
+        if (!find_mlp_fwd(k.prec, k.save)) return false;
+        const bool masks = k.save == FWD_SAVE_MASKS;
+        if (masks ? !k.pose : !find_mlp_bwd(k.prec, !k.pose, k.waves, k.save)) return false;
+        if (k.save != FWD_SAVE_Q8 && !find_mlp_bwd(k.prec, true, k.waves, masks ? (int)FWD_SAVE_PLANES : (int)FWD_SAVE_MASKS)) return false;
+    }
+    return true;
+}
+static_assert(mlp_tables_consistent(), "kernels.h: a fused MLP kernel is missing its forward, its pose / masks-only twin or a geometry");
+
+// the dispatch (mlp_launch.hip): a table lookup, 1 if there is no such kernel
+int launch_mlp_fwd(int prec, int save, const MlpFwdArgs& a, int grid, hipStream_t stream);
+int launch_mlp_bwd(int prec, bool pose, int save, int waves, const MlpBwdArgs& a, int grid, hipStream_t stream);
 
 struct WgradArgs {
     const void* save;          // saved activations (X operands)

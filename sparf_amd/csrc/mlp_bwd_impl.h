@@ -9,8 +9,9 @@
 // Math: SURVEY.md Appendix A "Backward" (autograd of
 // /root/reference/source/models/frequency_nerf.py:149-226).
 //
-// This file is the body of the translation units mlp_bwd*.hip (plane areas, one unit per precision / geometry; mlp_bwd_q8.hip: 8-bit areas)
-// and rays_bwd*.hip (ray-gradient-only passes: P = RaysOnly<...>, mlp_dev.h).
+// The kernel template and its launcher launch_mlp_bwd_t.  kernels.h lists the instances; the translation units mlp_bwd*.hip (plane areas, one
+// unit per precision / geometry; mlp_bwd_q8.hip: 8-bit areas) and rays_bwd*.hip (ray-gradient-only passes: P = RaysOnly<...>, mlp_dev.h) are
+// their explicit instantiations and nothing else, so that they compile in parallel: as one unit the six plane kernels took eleven minutes.
 #pragma once
 #include "kernels.h"
 #include "mlp_dev.h"
@@ -452,6 +453,14 @@ __global__ void __launch_bounds__(P::NWAVES * 64) mlp_bwd_kernel(MlpBwdArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (int i = 0; i < 10; ++i) g_prof_bwd[i] = pipe.prof.acc[i];
 #endif
+}
+
+// SAVE: what the forward of the pass left (kernels.h FWD_SAVE_*).  (The caller sizes the grid by CU count; the kernel strides over its own tiles.)
+template <int PREC, bool POSE, int WAVES, int SAVE> int launch_mlp_bwd_t(const MlpBwdArgs& a, int grid, hipStream_t stream) {
+    typedef typename DgradPolicy<PREC, WAVES, SAVE == FWD_SAVE_MASKS>::type P;
+    if (a.rows <= 0) return 0;
+    hipLaunchKernelGGL((mlp_bwd_kernel<PREC, POSE, P, SAVE == FWD_SAVE_Q8>), dim3(grid), dim3(P::NWAVES * 64), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 }  // namespace sparf

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "streams.h"
@@ -92,8 +93,8 @@ template <> struct Policy<PREC_X3> {
 #endif
 // Geometry of the bf16x3 data-gradient kernel: W = 8 waves (two per SIMD inside 256 VGPRs, 256-row workgroup tiles: 12-17 % faster per
 // row, mlp_bwd_impl.h bwd_layer_deferred) or W = 4 (one wave per SIMD with the whole register file, 128-row tiles, the forward
-// kernels' geometry).  Both are compiled into the library since round 6 (mlp_bwd_x3.hip / mlp_bwd_x3w4.hip) and api.hip picks one
-// per launch from the row count: a 512-ray step's coarse pass is 32 768 rows = 128 tiles of 256 rows -- half the chip idle for
+// kernels' geometry).  Both are compiled into the library since round 6 (mlp_bwd_x3.hip / mlp_bwd_x3w4.hip) and the plan of a pass picks
+// per launch from the row count (pass_plan.h plan_dgrad): a 512-ray step's coarse pass is 32 768 rows = 128 tiles of 256 rows -- half the chip idle for
 // a whole tile time -- but 256 tiles of 128 rows.  sparf_launch_kernel 3 / 4 pins one geometry at run time (A/B measurements).
 template <int W> struct PolicyX3DgradT {
     enum { PREC = PREC_X3, KJ = 8, CH = 8, FRAG_BYTES = 2048, LANE_BYTES = 16, G = group_g(PREC_X3), NWAVES = W, PREFETCH = (W == 8 ? 3 : 4),
@@ -111,14 +112,19 @@ template <int W> struct PolicyX3DgradT {
     static SP_DEV void set(B* v, int q, float x) { v[q >> 3][q & 7] = (__bf16)x; }
     static SP_DEV float get(const B* v, int q) { return (float)v[q >> 3][q & 7]; }
 };
-typedef PolicyX3DgradT<8> PolicyX3Dgrad;          // the 256-row geometry (and the one the 8-bit-area kernels keep)
-typedef PolicyX3DgradT<4> PolicyX3DgradW4;
 // Data gradient of a ray-gradient-only pass (layout.h AREA_MASKS; rays_bwd*.hip): the arithmetic and geometry of policy P, carried in the
 // policy class -- mlp_bwd_kernel reads the trait below -- so that the kernel template keeps its parameter list.  The kernel then
 // addresses the masks-only save area and issues none of the dY stores.
 template <class P> struct RaysOnly : P {};
 template <class P> struct rays_only { enum { value = 0 }; };
 template <class P> struct rays_only<RaysOnly<P>> { enum { value = 1 }; };
+// The policy class of the data-gradient kernel of a line of kernels.h' list: (precision, waves per workgroup, ray-gradient-only).
+// bf16 and fp32 run their forward's policy; bf16x3 the chain above in either geometry (the 8-bit-area kernels keep the 256-row one).
+template <int PREC, int WAVES, bool RAYS> struct DgradPolicy {
+    typedef std::conditional_t<PREC == PREC_X3, PolicyX3DgradT<WAVES>, Policy<PREC>> base;
+    static_assert(base::NWAVES == WAVES, "this precision has no data-gradient kernel of that geometry");
+    typedef std::conditional_t<RAYS, RaysOnly<base>, base> type;
+};
 
 // ------------------------------------------------------------------ wave-time accounting (SP_PROF builds only)
 // tools/kernel_bench.py prints where wave 0 of workgroup 0 of the forward kernel spends its cycles

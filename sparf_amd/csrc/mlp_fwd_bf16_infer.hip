@@ -1,6 +1,4 @@
 // Fused NeRF MLP forward, bf16 inference kernel; the code is mlp_fwd_impl.h.
-#define SP_FWD_PREC sparf::PREC_BF16
-#define SP_FWD_SAVE false
-#define SP_FWD_LAUNCHER launch_mlp_fwd_bf16_infer
-#define SP_FWD_PROF_EXPORT 0
 #include "mlp_fwd_impl.h"
+
+template int sparf::launch_mlp_fwd_t<sparf::PREC_BF16, sparf::FWD_INFER>(const sparf::MlpFwdArgs&, int, hipStream_t);

@@ -10,17 +10,14 @@
 // (compute_raw_density + forward), :47-69/:229-258 (encoding, c2f mask),
 // /root/reference/source/utils/camera.py:433-435 (p = c + r*t).
 //
-// This file is the body of one translation unit per kernel (mlp_fwd_{bf16,fp32,x3}_{train,train_q8,infer}.hip, rays_fwd_{bf16,fp32,x3}.hip),
-// compiled in parallel -- as one unit the kernel instantiations took many minutes.
+// The kernel template and its launcher launch_mlp_fwd_t.  kernels.h lists the instances; each is explicitly instantiated in a translation
+// unit of its own (mlp_fwd_{bf16,fp32,x3}_{train,train_q8,infer}.hip, rays_fwd_{bf16,fp32,x3}.hip: nothing but that line), compiled in
+// parallel -- as one unit the kernel instantiations took many minutes.
 #pragma once
 #include <utility>
 
 #include "kernels.h"
 #include "mlp_dev.h"
-
-#if !defined(SP_FWD_PREC) || !defined(SP_FWD_SAVE)
-#error "include from mlp_fwd_<precision>_<train|infer>.hip with SP_FWD_PREC / SP_FWD_SAVE defined"
-#endif
 
 namespace sparf {
 
@@ -468,16 +465,10 @@ __global__ void __launch_bounds__(Policy<PREC>::NWAVES * 64) mlp_fwd_kernel(MlpF
 #endif
 }
 
-int SP_FWD_LAUNCHER(const MlpFwdArgs& a, int grid, hipStream_t stream) {
+template <int PREC, int SAVE> int launch_mlp_fwd_t(const MlpFwdArgs& a, int grid, hipStream_t stream) {
     if (a.rows <= 0) return 0;
-    hipLaunchKernelGGL((mlp_fwd_kernel<SP_FWD_PREC, (int)SP_FWD_SAVE>), dim3(grid), dim3(Policy<SP_FWD_PREC>::NWAVES * 64), 0, stream, a);
+    hipLaunchKernelGGL((mlp_fwd_kernel<PREC, SAVE>), dim3(grid), dim3(Policy<PREC>::NWAVES * 64), 0, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 }  // namespace sparf
-
-#if defined(SP_PROF) && SP_FWD_PROF_EXPORT
-extern "C" int sparf_debug_prof(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(sparf::g_prof), 10 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif

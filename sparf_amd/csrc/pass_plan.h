@@ -11,17 +11,19 @@ namespace sparf {
 
 static constexpr int64_t kPartialFloats = wpartial_floats();      // (compile time: streams.h's constexpr enumeration loops are not re-run per call)
 
-static inline bool prec_ok(int p) { return p >= 0 && p < N_PREC; }
+static constexpr bool prec_ok(int p) { return p >= 0 && p < N_PREC; }
 // A pass's precision id may carry SPARF_SAVE_Q8 (sparf_hip.h): the arithmetic of `base`, save and gradient areas in the 8-bit format
-// (layout.h AREA_Q8); bf16-operand modes only.  Or SPARF_SAVE_MASKS: a ray-gradient-only pass of any base precision -- the save area
-// holds the ReLU mask words only (layout.h AREA_MASKS), the backward runs no weight gradient.  Not both.
-struct PassPrec { int base; bool q8, masks; int af; bool ok; };
-static inline PassPrec pass_prec(int p) {
-    PassPrec r;
+// (layout.h AREA_Q8); the modes that have such a forward kernel (kernels.h: the bf16-operand ones).  Or SPARF_SAVE_MASKS: a
+// ray-gradient-only pass of any base precision -- the save area holds the ReLU mask words only (layout.h AREA_MASKS), the backward
+// runs no weight gradient.  Not both.
+struct PassPrec { int base; bool q8, masks; int af; bool ok; int save; };      // save: what the training forward leaves (kernels.h FWD_SAVE_*)
+static constexpr PassPrec pass_prec(int p) {
+    PassPrec r{};
     r.base = p & ~(SPARF_SAVE_Q8 | SPARF_SAVE_MASKS);
     r.q8 = (p & SPARF_SAVE_Q8) != 0;
     r.masks = (p & SPARF_SAVE_MASKS) != 0;
-    r.ok = prec_ok(r.base) && (!r.q8 || r.base == PREC_BF16 || r.base == PREC_X3) && !(r.q8 && r.masks);
+    r.save = r.q8 ? FWD_SAVE_Q8 : r.masks ? FWD_SAVE_MASKS : FWD_SAVE_PLANES;
+    r.ok = prec_ok(r.base) && (!r.q8 || find_mlp_fwd(r.base, FWD_SAVE_Q8)) && !(r.q8 && r.masks);
     r.af = r.masks ? (int)AREA_MASKS : area_format(r.ok ? r.base : 0, r.q8);
     return r;
 }
@@ -129,7 +131,7 @@ static inline BwdWs bwd_ws_layout(int af, int nrays, int nsamp, int pose) {     
 // (row routing is compiled into the fp32 forward kernels, mlp_fwd_impl.h); main precision: a bf16-plane save layout (bf16, bf16x3)
 // far_count = -1: far TILES by value (inference only): 128-row tiles whose largest depth sample exceeds far_thr go to far_prec, the
 // others to prec; needs nsamp % 32 == 0 (a 32-row wave tile then lies inside one ray, whose samples increase)
-static inline bool far_ok(int far_count, int far_prec, int nsamp, int prec) {
+static constexpr bool far_ok(int far_count, int far_prec, int nsamp, int prec) {
     if (far_count == 0) return true;
     if (far_prec != PREC_FP32 || prec == PREC_FP32) return false;
     // tile routing decides per WORKGROUP tile (nwaves x 32 rows): both launches must cut the rows into the same tiles, or a tile of
@@ -204,7 +206,7 @@ static inline int plan_forward(const sparf_pass_fwd_t* p, FwdPlan* f) {
     if (p->far_count && (!p->far_packed || (p->save != nullptr && !p->far_ws) || (p->far_prec != prec && !p->far_venc_ws))) return 1;
     if (p->far_count == -1 && p->save != nullptr) return 1;            // tile routing: inference passes only
     f->masks = pp.masks;
-    f->main = FwdLaunch{prec, !p->save ? FWD_INFER : pp.q8 ? FWD_SAVE_Q8 : pp.masks ? FWD_SAVE_MASKS : FWD_SAVE_PLANES, mlp_fwd_args(p)};
+    f->main = FwdLaunch{prec, p->save ? pp.save : (int)FWD_INFER, mlp_fwd_args(p)};
     f->far_kind = p->far_count == 0 ? FAR_NONE : p->far_count == -1 ? FAR_TILES : FAR_ROWS;
     f->far_setup = f->far_kind != FAR_NONE && p->far_prec != prec;
     f->far = FwdLaunch{p->far_prec, FWD_INFER, f->main.a};
@@ -237,6 +239,11 @@ static inline int plan_forward(const sparf_pass_fwd_t* p, FwdPlan* f) {
 }
 
 // ---- backward
+struct BwdLaunch {                   // one launch_mlp_bwd of kernel k: on mlp_grid(k->prec, n) workgroups
+    const MlpBwdKernel* k;
+    MlpBwdArgs a;
+    int64_t n;                       // rows of the launch
+};
 struct BwdPlan {
     PassPrec pp;
     bool pose;                       // ray gradients wanted (d_center and d_dir); always, in a ray-gradient-only pass (pp.masks)
@@ -246,15 +253,34 @@ struct BwdPlan {
     bool no_grad;                    // segmented pass none of whose segments has an upstream gradient: every result is zero
     BwdWs ws;
     Split split;                     // of the active rows (never more splits than ws holds partial blocks)
-    int64_t rows8;                   // data gradient: the leading active rows that go through the 8-wave kernel (bf16x3 with plane
-                                     // areas: x3_dgrad_rows8; every other mode: all of them)
     CompositeBwdArgs c;
-    MlpBwdArgs m;
+    MlpBwdArgs m;                    // data gradient over all active rows, cut into
+    BwdLaunch dgrad[2];              // its ndgrad launches (plan_dgrad)
+    int ndgrad;
     WgradArgs g;
     RayReduceArgs r;                 // only if pose
 };
-// -> ABI status code.  whole_pass (sparf_launch_kernel): the kernels cover rows [0, nrays * nsamp) whatever the segment table says
-static inline int plan_backward(const sparf_pass_bwd_t* p, bool whole_pass, BwdPlan* b) {
+// The data-gradient launches of a plan over its active rows.  A mode whose kernel comes in two geometries (kernels.h: bf16x3 over plane or
+// masks-only areas) sends the leading x3_dgrad_rows8 rows through the 8-wave one and the rest, if any, through the 4-wave one behind it;
+// every other mode all rows through the one it has.  `pin` (measurement: sparf_launch_kernel 3 / 4) = 8 | 4 forces one of the two for
+// the whole range; 0: the plan's choice.
+static inline void plan_dgrad(BwdPlan* b, int pin) {
+    const MlpBwdKernel *k8 = find_mlp_bwd(b->pp.base, b->pose, 8, b->pp.save), *k4 = find_mlp_bwd(b->pp.base, b->pose, 4, b->pp.save);
+    const int64_t rows = b->row1 - b->row0;
+    const int64_t rows8 = !k4 ? rows : !k8 ? 0 : pin == 8 ? rows : pin == 4 ? 0 : x3_dgrad_rows8(rows);
+    b->ndgrad = 0;
+    if (rows8 > 0) {
+        BwdLaunch& l = b->dgrad[b->ndgrad++] = BwdLaunch{k8, b->m, rows8};
+        l.a.rows = b->row0 + rows8;
+    }
+    if (rows8 < rows) {
+        BwdLaunch& l = b->dgrad[b->ndgrad++] = BwdLaunch{k4, b->m, rows - rows8};
+        l.a.row_begin = b->row0 + rows8;
+    }
+}
+// -> ABI status code.  whole_pass (sparf_launch_kernel): the kernels cover rows [0, nrays * nsamp) whatever the segment table says;
+// pin: plan_dgrad's
+static inline int plan_backward(const sparf_pass_bwd_t* p, bool whole_pass, BwdPlan* b, int pin = 0) {
     if (!p) return 1;
     const PassPrec pp = b->pp = pass_prec(p->prec);
     if (!pp.ok || p->nrays < 0 || p->nsamp <= 0) return 1;
@@ -300,8 +326,8 @@ static inline int plan_backward(const sparf_pass_bwd_t* p, bool whole_pass, BwdP
     c.ray_base = ray0;
     c.nrays = ray1 - ray0;
     b->split = split_of_range(rows, row1 - row0);
-    b->rows8 = pp.base == PREC_X3 && !pp.q8 ? x3_dgrad_rows8(row1 - row0) : row1 - row0;
     b->m = MlpBwdArgs{(const char*)p->packed, p->c2f, p->center, p->dir, p->t, row1, p->nsamp, p->save, ws + w.grad, d_sigma, d_z, dp, dv, row0, rows};
+    plan_dgrad(b, pin);
     b->g = WgradArgs{p->save, ws + w.grad, row1, b->split.rows_per_split, (float*)(ws + w.partial), row0};
     if (pose) {
         b->r = RayReduceArgs{ray1 - ray0, p->nsamp, p->t, dp, dv, p->dir, p->raylen, d_len, p->c2f + 10, p->d_center, p->d_dir, ray0};
@@ -309,5 +335,25 @@ static inline int plan_backward(const sparf_pass_bwd_t* p, bool whole_pass, BwdP
     }
     return 0;
 }
+
+// A plan that succeeds names only kernels that exist (kernels.h): every precision id pass_prec accepts has its inference and its
+// training forward and, with and without pose gradients (ray-gradient-only: with), a data-gradient kernel in one of the two geometries
+// plan_dgrad looks for; every far precision far_ok accepts has the forwards a far launch can be (inference, plane saves, mask words).
+constexpr bool plan_kernels_exist() {
+    const int flags[] = {0, SPARF_SAVE_Q8, SPARF_SAVE_MASKS};
+    for (int base = 0; base < N_PREC; ++base) {
+        for (int f : flags) {
+            const PassPrec pp = pass_prec(base | f);
+            if (!pp.ok) continue;
+            if (!find_mlp_fwd(base, FWD_INFER) || !find_mlp_fwd(base, pp.save)) return false;
+            for (int pose = pp.masks ? 1 : 0; pose < 2; ++pose)
+                if (!find_mlp_bwd(base, pose != 0, 8, pp.save) && !find_mlp_bwd(base, pose != 0, 4, pp.save)) return false;
+        }
+        for (int far = 0; far < N_PREC; ++far)
+            if (far_ok(1, far, 2, base) && !(find_mlp_fwd(far, FWD_INFER) && find_mlp_fwd(far, FWD_SAVE_PLANES) && find_mlp_fwd(far, FWD_SAVE_MASKS))) return false;
+    }
+    return true;
+}
+static_assert(plan_kernels_exist(), "pass_plan.h accepts a pass for which kernels.h lists no kernel");
 
 }  // namespace sparf

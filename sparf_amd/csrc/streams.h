@@ -1,6 +1,6 @@
 // Weight-fragment streams: the order in which the fused MLP kernels consume A-operand
 // fragments, cut into LDS-sized chunks.  Host (table builder, pack.hip) and device
-// (mlp_fwd.hip / mlp_bwd.hip) both derive chunk ids and sizes from the constexpr functions
+// (mlp_fwd_impl.h / mlp_bwd_impl.h) both derive chunk ids and sizes from the constexpr functions
 // here, so they cannot disagree.
 //
 // A fragment is one MFMA A operand: 32 C-rows x (2*KJ) contraction slots, stored

@@ -10,6 +10,7 @@ What is pinned, and where the numbers come from (DESIGN 3.2 "instruction stream"
 The tile body is fully unrolled, so the static counts are per tile and wave."""
 import importlib.util
 import os
+import subprocess
 
 import pytest
 
@@ -21,10 +22,16 @@ DGRAD_POSE = "_ZN5sparf14mlp_bwd_kernelILi2ELb1ENS_14PolicyX3DgradTILi8EEELb0EEE
 
 
 @pytest.fixture(scope="module")
-def figs():
+def stream():
     spec = importlib.util.spec_from_file_location("kernel_stream", os.path.join(ROOT, "tools", "kernel_stream.py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
+    return m
+
+
+@pytest.fixture(scope="module")
+def figs(stream):
+    m = stream
     out = {}
     for unit in m.MLP_UNITS:
         for k, f in m.figures(unit).items():
@@ -113,3 +120,22 @@ def test_every_mlp_kernel_keeps_its_registers_and_parks_no_scalars(figs):
                 and f["sgpr_spill_count"] <= parked):
             bad[key] = f
     assert not bad, bad
+
+
+def test_every_kernel_instance_is_compiled_once_and_the_dispatch_unit_holds_none(stream, figs, tmp_path):
+    """csrc/kernels.h lists the instances of mlp_fwd_kernel / mlp_bwd_kernel, each unit instantiates its own explicitly, and the dispatch
+    unit looks the launchers up without seeing the templates' definitions.  A definition that becomes visible where it should not
+    compiles kernels a second time -- silently, and for many minutes."""
+    d = str(tmp_path)
+    owners = {}
+    for unit, k in (key for key in figs if isinstance(key, tuple)):
+        owners.setdefault(k, []).append(unit)
+    for unit in stream.B.RAYS_UNITS:
+        for k in stream.notes_of(stream.code_object(stream.object_of(unit, d), d)):
+            owners.setdefault(k, []).append(unit)
+    assert set(stream.MLP_UNITS) | set(stream.B.RAYS_UNITS) == set(stream.B.FUSED_UNITS)
+    assert all("mlp_fwd_kernel" in k or "mlp_bwd_kernel" in k for k in owners), owners
+    assert len(owners) == len(ALL_KERNELS) + len(stream.B.RAYS_UNITS), sorted(owners)        # (a ray-gradient-only unit holds one kernel)
+    assert all(len(units) == 1 for units in owners.values()), {k: u for k, u in owners.items() if len(u) != 1}
+    with pytest.raises(subprocess.CalledProcessError):                                        # no gfx950 code object in it at all
+        stream.code_object(stream.object_of(stream.B.MLP_DISPATCH, d), d)

@@ -1,7 +1,7 @@
 """Static instruction-stream figures of the built fused-MLP kernels: what the compiler made of a tile, per wave.
 
     python tools/kernel_stream.py [translation unit ...]        (default: the two config-1 units of the bf16x3 mode; `all` = every
-                                                                 unit built from mlp_fwd_impl.h / mlp_bwd_impl.h)
+                                                                 fused MLP kernel unit but the ray-gradient-only ones)
     python tools/kernel_stream.py diff <object dir A> <object dir B>     (every kernel of every unit both directories hold: IDENTICAL, or
                                                                  DIFFER with what differs; e.g. sparf_amd/csrc_<tag> of tools/build_variant.py
                                                                  against sparf_amd/csrc/build -- a refactor's proof of "same machine code")
@@ -158,8 +158,8 @@ def compare_listings(a, b):
     return out
 
 
-# every translation unit built from mlp_dev.h + mlp_fwd_impl.h / mlp_bwd_impl.h
-MLP_UNITS = [u for u in B.SOURCES if u.startswith(("mlp_fwd_", "mlp_bwd"))]
+# the fused MLP kernel units of passes with parameter gradients (the ray-gradient-only ones: tests/test_rays_only_cpu.py)
+MLP_UNITS = [u for u in B.FUSED_UNITS if u not in B.RAYS_UNITS]
 
 
 def figures(unit):
