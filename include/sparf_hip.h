@@ -132,6 +132,40 @@ int sparf_ray_gen_backward(const float* pose, const float* intr, const float* pi
                            int width, int nimg, int nrays, const float* d_center, const float* d_ray, float* d_pose,
                            void* stream);
 
+/* ---- pose parameterisations --------------------------------------------
+ * The bodies of the pose chain of a trainer, one launch per direction each; parameters,
+ * optimiser and autograd graph stay the caller's.  One pose per thread, double arithmetic on
+ * the fp32 inputs, one rounding per stored value.  n = number of poses; n == 0 returns 0 and
+ * launches nothing, n < 0 or a missing required pointer returns 1 before any HIP call.
+ *
+ * se(3): xi[n][6] = (w, u).  refine = [R | V u] with R = I + A wx + B wx^2,
+ * V = I + B wx + C wx^2 and A, B, C the TRUNCATED series of source/utils/camera.py:180-205
+ * (nth = 10: 11 terms in |w|^2), as Lie.se3_to_SE3 evaluates them (:142-157) -- polynomials,
+ * not sin / cos, so there is no singularity at w = 0.  With base[n][3][4] the result is
+ * Pose.compose([refine, base]) (:100-115): R = R_base R_refine, t = R_base t_refine + t_base;
+ * without it pose_out = refine.  refine_out (NULL ok) also receives refine.  The backward is
+ * the exact vector-Jacobian product of that polynomial function from d_pose and, NULL ok, an
+ * upstream gradient on refine; d_base (NULL ok) needs base.
+ *
+ * compose: out = Pose.compose_pair_b_at_a(a, b) (:108-115), R = R_b R_a, t = R_b t_a + t_b.
+ *
+ * d9: d9[n][9] = (t, r1, r2) in the order of pose_to_d9
+ * (source/models/poses_models/two_columns.py:23-39: the translation, then the two first ROWS
+ * of the rotation).  R = r6d2mat(r1, r2) (:42-62), Gram-Schmidt with F.normalize's
+ * v / max(|v|, 1e-12); pose = [R | t]; invert != 0: Pose.invert of it (camera.py:92-98, the
+ * transpose form) = [R^T | -R^T t]. */
+int sparf_pose_se3_forward(const float* xi, const float* base /*NULL ok*/, int n,
+                           float* refine_out /*NULL ok*/, float* pose_out, void* stream);
+int sparf_pose_se3_backward(const float* xi, const float* base, int n,
+                            const float* d_pose, const float* d_refine /*NULL ok*/,
+                            float* d_xi, float* d_base /*NULL ok*/, void* stream);
+int sparf_pose_compose_forward(const float* a, const float* b, int n, float* out, void* stream);
+int sparf_pose_compose_backward(const float* a, const float* b, int n, const float* d_out,
+                                float* d_a, float* d_b, void* stream);
+int sparf_pose_d9_forward(const float* d9, int invert, int n, float* pose_out, void* stream);
+int sparf_pose_d9_backward(const float* d9, int invert, int n, const float* d_pose,
+                           float* d_d9, void* stream);
+
 /* ---- optimiser step ----------------------------------------------------
  * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) (source/training/base.py:96-97,
  * engine after_backward; skipped when max_norm <= 0) followed by torch.optim.Adam.step()

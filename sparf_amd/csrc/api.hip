@@ -9,6 +9,13 @@ int launch_c2f(const float* progress, int has_c2f, float c2f_start, float c2f_en
 int launch_calib_mfma(int iters, float* sink, int grid, hipStream_t s);
 int launch_calib_hbm(const void* src, void* dst, int64_t bytes, int mode, float* sink, int grid, hipStream_t s);
 int64_t calib_mfma_flops(int iters, int grid);
+// pose.hip: one thread per pose, n > 0
+int launch_pose_se3_fwd(const float* xi, const float* base, int n, float* refine_out, float* pose_out, hipStream_t s);
+int launch_pose_se3_bwd(const float* xi, const float* base, int n, const float* d_pose, const float* d_refine, float* d_xi, float* d_base, hipStream_t s);
+int launch_pose_compose_fwd(const float* a, const float* b, int n, float* out, hipStream_t s);
+int launch_pose_compose_bwd(const float* a, const float* b, int n, const float* d_out, float* d_a, float* d_b, hipStream_t s);
+int launch_pose_d9_fwd(const float* d9, int invert, int n, float* pose_out, hipStream_t s);
+int launch_pose_d9_bwd(const float* d9, int invert, int n, const float* d_pose, float* d_d9, hipStream_t s);
 }  // namespace sparf
 
 using namespace sparf;
@@ -114,6 +121,43 @@ int sparf_ray_gen_backward(const float* pose, const float* intr, const float* pi
     if (ray_idx && width <= 0) return 1;
     RayGenArgs a{nimg, nrays, width, per_image, pose, intr, pixels, ray_idx, nullptr, nullptr};
     return launch_ray_gen_bwd(a, d_center, d_ray, d_pose, (hipStream_t)stream);
+}
+
+// ---- pose parameterisations (sparf_hip.h): n == 0 launches nothing, whatever the pointers; then the argument checks
+// camera.py:142-157 Lie.se3_to_SE3 with its series :180-205, then Pose.compose([refine, base]) :100-115
+int sparf_pose_se3_forward(const float* xi, const float* base, int n, float* refine_out, float* pose_out, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !xi || !pose_out) return 1;
+    return launch_pose_se3_fwd(xi, base, n, refine_out, pose_out, (hipStream_t)stream);
+}
+// what autograd derives from camera.py:142-157, :180-205 and :108-115
+int sparf_pose_se3_backward(const float* xi, const float* base, int n, const float* d_pose, const float* d_refine, float* d_xi, float* d_base,
+                            void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !xi || !d_pose || !d_xi || (d_base && !base)) return 1;
+    return launch_pose_se3_bwd(xi, base, n, d_pose, d_refine, d_xi, d_base, (hipStream_t)stream);
+}
+// camera.py:108-115 Pose.compose_pair_b_at_a
+int sparf_pose_compose_forward(const float* a, const float* b, int n, float* out, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !a || !b || !out) return 1;
+    return launch_pose_compose_fwd(a, b, n, out, (hipStream_t)stream);
+}
+int sparf_pose_compose_backward(const float* a, const float* b, int n, const float* d_out, float* d_a, float* d_b, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !a || !b || !d_out || !d_a || !d_b) return 1;
+    return launch_pose_compose_bwd(a, b, n, d_out, d_a, d_b, (hipStream_t)stream);
+}
+// two_columns.py:42-62 r6d2mat and the concatenation of :147-148 / :177-178; invert: camera.py:92-98 Pose.invert
+int sparf_pose_d9_forward(const float* d9, int invert, int n, float* pose_out, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !d9 || !pose_out) return 1;
+    return launch_pose_d9_fwd(d9, invert, n, pose_out, (hipStream_t)stream);
+}
+int sparf_pose_d9_backward(const float* d9, int invert, int n, const float* d_pose, float* d_d9, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !d9 || !d_pose || !d_d9) return 1;
+    return launch_pose_d9_bwd(d9, invert, n, d_pose, d_d9, (hipStream_t)stream);
 }
 
 int64_t sparf_adam_workspace_floats(void) { return 256; }

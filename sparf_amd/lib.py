@@ -97,6 +97,12 @@ EXPORTS = {
     "sparf_ray_gen_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sparf_ray_gen_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    "sparf_pose_se3_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "sparf_pose_se3_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sparf_pose_compose_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "sparf_pose_compose_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sparf_pose_d9_forward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sparf_pose_d9_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sparf_adam_workspace_floats": (c_int64, []),
     "sparf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p]),

@@ -566,6 +566,115 @@ def photometric_loss(rgb, target, rgb_fine=None, huber=False, delta=0.5):
     return PhotometricLoss.apply(rgb, rgb_fine, target, 1 if huber else 0, delta)
 
 
+# ---------------------------------------------------------------------------------------------- pose parameterisations
+def _pose_call(name, dev, *args):
+    """one entry point of the pose family on the current stream: no host synchronisation, no readback"""
+    lib = L.load()
+    with L.on(dev):
+        L.check(getattr(lib, name)(*args, L.stream_ptr(dev)), name)
+
+
+def _pose_empty(like, *shape):
+    return torch.empty(*shape, device=like.device, dtype=torch.float32)
+
+
+class Se3Pose(torch.autograd.Function):
+    """camera.lie.se3_to_SE3 (camera.py:142-157, the truncated series of :180-205) and, with a base, camera.pose.compose([refine, base])
+    (:100-115) in one launch per direction.  xi [n,6] = (w, u), base [n,3,4] or None, want_refine: also return refine [n,3,4].
+    -> (pose [n,3,4], refine | None); without a base the pose IS the refinement and refine is None."""
+
+    @staticmethod
+    def forward(ctx, xi, base, want_refine):
+        dev = xi.device
+        L.require_gpu(dev)
+        x = _f32(xi)
+        b = _f32(base) if base is not None else None
+        n = x.shape[0]
+        pose = _pose_empty(x, n, 3, 4)
+        refine = _pose_empty(x, n, 3, 4) if (want_refine and b is not None) else None
+        P = L.ptr
+        _pose_call("sparf_pose_se3_forward", dev, P(x), P(b), n, P(refine), P(pose))
+        ctx.save_for_backward(x, b)
+        ctx.set_materialize_grads(False)
+        return pose, refine
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pose, g_refine):
+        x, b = ctx.saved_tensors
+        need_xi, need_base = ctx.needs_input_grad[0], b is not None and ctx.needs_input_grad[1]
+        if (g_pose is None and g_refine is None) or not (need_xi or need_base):
+            return None, None, None
+        n = x.shape[0]
+        gp = _f32(g_pose) if g_pose is not None else torch.zeros(n, 3, 4, device=x.device, dtype=torch.float32)
+        gr = _f32(g_refine) if g_refine is not None else None
+        d_xi = _pose_empty(x, n, 6)
+        d_base = _pose_empty(x, n, 3, 4) if need_base else None
+        P = L.ptr
+        _pose_call("sparf_pose_se3_backward", x.device, P(x), P(b), n, P(gp), P(gr), P(d_xi), P(d_base))
+        return d_xi if need_xi else None, d_base, None
+
+
+class ComposePose(torch.autograd.Function):
+    """camera.pose.compose_pair_b_at_a (camera.py:108-115): a, b [n,3,4] -> b o a = [R_b R_a | R_b t_a + t_b]."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        dev = a.device
+        L.require_gpu(dev)
+        pa, pb = _f32(a), _f32(b)
+        n = pa.shape[0]
+        out = _pose_empty(pa, n, 3, 4)
+        P = L.ptr
+        _pose_call("sparf_pose_compose_forward", dev, P(pa), P(pb), n, P(out))
+        ctx.save_for_backward(pa, pb)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pa, pb = ctx.saved_tensors
+        if g is None or not any(ctx.needs_input_grad):
+            return None, None
+        n = pa.shape[0]
+        d_a, d_b = _pose_empty(pa, n, 3, 4), _pose_empty(pa, n, 3, 4)
+        P = L.ptr
+        _pose_call("sparf_pose_compose_backward", pa.device, P(pa), P(pb), n, P(_f32(g)), P(d_a), P(d_b))
+        return d_a if ctx.needs_input_grad[0] else None, d_b if ctx.needs_input_grad[1] else None
+
+
+class D9Pose(torch.autograd.Function):
+    """The 6D rotation model (two_columns.py:42-62 r6d2mat and the concatenation of :177-178): d9 [n,9] = (t, r1, r2) in
+    pose_to_d9's order -> [R | t] [n,3,4], or with `invert` camera.pose.invert of it (camera.py:92-98)."""
+
+    @staticmethod
+    def forward(ctx, d9, invert):
+        dev = d9.device
+        L.require_gpu(dev)
+        x = _f32(d9)
+        n = x.shape[0]
+        pose = _pose_empty(x, n, 3, 4)
+        P = L.ptr
+        _pose_call("sparf_pose_d9_forward", dev, P(x), int(bool(invert)), n, P(pose))
+        ctx.save_for_backward(x)
+        ctx.invert = int(bool(invert))
+        ctx.set_materialize_grads(False)
+        return pose
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None
+        n = x.shape[0]
+        d_d9 = _pose_empty(x, n, 9)
+        P = L.ptr
+        _pose_call("sparf_pose_d9_backward", x.device, P(x), ctx.invert, n, P(_f32(g)), P(d_d9))
+        return d_d9, None
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
 class Composite(torch.autograd.Function):
     """NeRF.composite (frequency_nerf.py:283-343) on caller-built per-sample values (C ABI 6 sparf_composite_forward / _backward):
