@@ -166,6 +166,52 @@ int sparf_pose_d9_forward(const float* d9, int invert, int n, float* pose_out, v
 int sparf_pose_d9_backward(const float* d9, int invert, int n, const float* d_pose,
                            float* d_d9, void* stream);
 
+/* ---- correspondence loss ------------------------------------------------
+ * The re-projection terms of source/training/core/corres_loss.py, each with its loss, stats,
+ * valid mask and gradient seeds from ONE call; the sampler, the renders and the autograd
+ * graph stay the caller's.  One term i -> j over n matches
+ * (compute_render_and_repro_loss_w_repro_thres :50-95; batch_project_to_other_img,
+ * source/utils/geometry/batched_geometry_utils.py:199-228; compute_diff_loss,
+ * source/training/core/base_losses.py:197-224), in the reference's operation order:
+ *   x = K_i^-1 [p_i, 1] d_i (closed-form inverse of a general 3x3);  h = T [x, 1];
+ *   X = h[0:3] / (h[3] + 1e-6);  y = K_j X;  uv = y[0:2] / (y[2] + 1e-6);  e = uv - q_j;
+ *   valid = (|e| <= pix_thresh, if pix_check) & (|d_j - X[2]| / (d_j + 1e-6) <= depth_thresh,
+ *   if depth_check);  l = sum_c huber_1(e_c) | sum_c |e_c| | sum_c e_c^2 | |e|  for loss_type
+ *   0 huber, 1 l1, 2 mse, 3 epe;  loss = sum_k l_k w_k valid_k / (#valid + 1e-6).
+ * All per-match arithmetic is double on the fp32 inputs, every sum is accumulated in double in
+ * a fixed order (no atomics: two calls on the same inputs give the same bits), each stored
+ * value is rounded once.  The checks are detached: gradients go to depth_i and T only.
+ *   out[4] = loss, perc_val_pix_rep, perc_val_depth_rep (0 for a check that is off), and the
+ *   mean of depth_i (of the first term: depth_in_corr_loss of corres_loss.py:186).
+ *   d_depth_i[n], d_T[16] (row 3 carries what the + 1e-6 of the division lets through),
+ *   valid[n] (bytes, 0 / 1): NULL ok.  weights[n]: NULL = 1.  depth_j: NULL ok without the
+ *   depth check.
+ * sparf_reproj_pair_loss is compute_loss_on_image_pair :183-219 for one view pair: from the
+ * two w2c poses [3][4] it forms T_self2other = P_other pose_inverse_4x4(P_self)
+ * (source/utils/camera.py:37-61) and its inverse, bottom rows exactly [0,0,0,1]; evaluates
+ * self -> other and other -> self on the coarse depths and, if both fine depths are given,
+ * on those too; out[0] = their sum / 2 (/ 4), out[1..2] the stats of the LAST term (the
+ * reference overwrites stats_dict), out[3] = mean(depth_self).  Seeds (NULL ok each): every
+ * depth[n], both poses [3][4] through the VJP of the two compositions.
+ * workspace: sparf_reproj_workspace_bytes(n) bytes (0 up to 4096 matches: one workgroup, one
+ * launch; above, partial totals of up to 64 workgroups per term, two launches; NULL = the
+ * one-workgroup path at any n).  n == 0 launches no kernel and zeroes out, d_T and d_pose.
+ * Returns 1 before any HIP call for n < 0, an unknown loss_type, the depth check without
+ * depth_j, fine depths (or their seeds) for one view only, or a missing required pointer. */
+int64_t sparf_reproj_workspace_bytes(int n);
+int sparf_reproj_loss(const float* pixels_i, const float* depth_i, const float* K_i, const float* pixels_j,
+                      const float* depth_j /*NULL ok*/, const float* K_j, const float* T_itoj, const float* weights /*NULL ok*/,
+                      int n, int loss_type, int pix_check, float pix_thresh, int depth_check, float depth_thresh,
+                      float* out, float* d_depth_i /*NULL ok*/, float* d_T /*NULL ok*/, unsigned char* valid /*NULL ok*/,
+                      void* workspace /*NULL ok*/, void* stream);
+int sparf_reproj_pair_loss(const float* pixels_self, const float* pixels_other, const float* depth_self, const float* depth_other,
+                           const float* depth_fine_self /*NULL ok*/, const float* depth_fine_other /*NULL ok*/,
+                           const float* K_self, const float* K_other, const float* pose_self, const float* pose_other,
+                           const float* weights /*NULL ok*/, int n, int loss_type, int pix_check, float pix_thresh,
+                           int depth_check, float depth_thresh, float* out, float* d_depth_self, float* d_depth_other,
+                           float* d_depth_fine_self, float* d_depth_fine_other, float* d_pose_self, float* d_pose_other,
+                           void* workspace /*NULL ok*/, void* stream);
+
 /* ---- optimiser step ----------------------------------------------------
  * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) (source/training/base.py:96-97,
  * engine after_backward; skipped when max_norm <= 0) followed by torch.optim.Adam.step()

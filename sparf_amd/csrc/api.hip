@@ -1,6 +1,7 @@
 // C ABI of libsparf_hip.so (see include/sparf_hip.h): argument checking, workspace
 // carving and kernel sequencing on the caller's stream.  No allocation, no global state.
 #include "pass_plan.h"
+#include "reproj.h"
 
 namespace sparf {
 int build_tables(int prec, int32_t* out);
@@ -16,6 +17,9 @@ int launch_pose_compose_fwd(const float* a, const float* b, int n, float* out, h
 int launch_pose_compose_bwd(const float* a, const float* b, int n, const float* d_out, float* d_a, float* d_b, hipStream_t s);
 int launch_pose_d9_fwd(const float* d9, int invert, int n, float* pose_out, hipStream_t s);
 int launch_pose_d9_bwd(const float* d9, int invert, int n, const float* d_pose, float* d_d9, hipStream_t s);
+// reproj.hip: n > 0
+int64_t reproj_workspace_bytes(int n);
+int launch_reproj(const ReprojArgs& a, hipStream_t s);
 }  // namespace sparf
 
 using namespace sparf;
@@ -158,6 +162,59 @@ int sparf_pose_d9_backward(const float* d9, int invert, int n, const float* d_po
     if (n == 0) return 0;
     if (n < 0 || !d9 || !d_pose || !d_d9) return 1;
     return launch_pose_d9_bwd(d9, invert, n, d_pose, d_d9, (hipStream_t)stream);
+}
+
+// ---- correspondence loss (sparf_hip.h): every argument check comes before any HIP call; n == 0 launches no kernel
+static inline bool reproj_opts_ok(int n, int loss_type, const float* out) {
+    return n >= 0 && n <= (1 << 30) && loss_type >= 0 && loss_type < REPROJ_LOSS_TYPES && out;
+}
+static int reproj_zero(float* p, int floats, hipStream_t s) {
+    return !p || hipMemsetAsync(p, 0, (size_t)floats * sizeof(float), s) == hipSuccess ? 0 : 2;
+}
+int64_t sparf_reproj_workspace_bytes(int n) { return reproj_workspace_bytes(n); }
+// corres_loss.py:50-95 compute_render_and_repro_loss_w_repro_thres: batched_geometry_utils.py:199-228 batch_project_to_other_img,
+// the two detached checks, base_losses.py:197-224 compute_diff_loss -- and what autograd derives from them for depth_i and T
+int sparf_reproj_loss(const float* pixels_i, const float* depth_i, const float* K_i, const float* pixels_j, const float* depth_j,
+                      const float* K_j, const float* T_itoj, const float* weights, int n, int loss_type, int pix_check, float pix_thresh,
+                      int depth_check, float depth_thresh, float* out, float* d_depth_i, float* d_T, unsigned char* valid, void* workspace,
+                      void* stream) {
+    if (!reproj_opts_ok(n, loss_type, out) || (depth_check && !depth_j)) return 1;
+    if (n > 0 && (!pixels_i || !depth_i || !K_i || !pixels_j || !K_j || !T_itoj)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) return reproj_zero(out, 4, s) | reproj_zero(d_T, 16, s);
+    ReprojArgs a{};
+    a.n = n; a.nterms = 1; a.loss_type = loss_type; a.pix_check = pix_check != 0; a.depth_check = depth_check != 0; a.pair = 0;
+    a.pix_thresh = pix_thresh; a.depth_thresh = depth_thresh;
+    a.K[0] = K_i; a.K[1] = K_j; a.T = T_itoj; a.weights = weights;
+    a.term[0] = ReprojTerm{pixels_i, depth_i, pixels_j, depth_j, d_depth_i, 0, 1, 0};
+    a.out = out; a.valid = valid; a.d_T = d_T; a.ws = (double*)workspace;
+    return launch_reproj(a, s);
+}
+// corres_loss.py:183-219 of compute_loss_on_image_pair: T_self2other = P_other pose_inverse_4x4(P_self) (camera.py:37-61), its inverse,
+// the two (four with depth_fine) terms, their mean, stats_dict as that call order leaves it -- and the gradients to every depth and
+// to both poses
+int sparf_reproj_pair_loss(const float* pixels_self, const float* pixels_other, const float* depth_self, const float* depth_other,
+                           const float* depth_fine_self, const float* depth_fine_other, const float* K_self, const float* K_other,
+                           const float* pose_self, const float* pose_other, const float* weights, int n, int loss_type, int pix_check,
+                           float pix_thresh, int depth_check, float depth_thresh, float* out, float* d_depth_self, float* d_depth_other,
+                           float* d_depth_fine_self, float* d_depth_fine_other, float* d_pose_self, float* d_pose_other, void* workspace,
+                           void* stream) {
+    if (!reproj_opts_ok(n, loss_type, out)) return 1;
+    if ((depth_fine_self != nullptr) != (depth_fine_other != nullptr)) return 1;
+    if (!depth_fine_self && (d_depth_fine_self || d_depth_fine_other)) return 1;
+    if (n > 0 && (!pixels_self || !pixels_other || !depth_self || !depth_other || !K_self || !K_other || !pose_self || !pose_other)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) return reproj_zero(out, 4, s) | reproj_zero(d_pose_self, 12, s) | reproj_zero(d_pose_other, 12, s);
+    ReprojArgs a{};
+    a.n = n; a.nterms = depth_fine_self ? 4 : 2; a.loss_type = loss_type; a.pix_check = pix_check != 0; a.depth_check = depth_check != 0; a.pair = 1;
+    a.pix_thresh = pix_thresh; a.depth_thresh = depth_thresh;
+    a.K[0] = K_self; a.K[1] = K_other; a.pose[0] = pose_self; a.pose[1] = pose_other; a.weights = weights;
+    a.term[0] = ReprojTerm{pixels_self, depth_self, pixels_other, depth_other, d_depth_self, 0, 1, 0};
+    a.term[1] = ReprojTerm{pixels_other, depth_other, pixels_self, depth_self, d_depth_other, 1, 0, 1};
+    a.term[2] = ReprojTerm{pixels_self, depth_fine_self, pixels_other, depth_fine_other, d_depth_fine_self, 0, 1, 0};
+    a.term[3] = ReprojTerm{pixels_other, depth_fine_other, pixels_self, depth_fine_self, d_depth_fine_other, 1, 0, 1};
+    a.out = out; a.d_pose[0] = d_pose_self; a.d_pose[1] = d_pose_other; a.ws = (double*)workspace;
+    return launch_reproj(a, s);
 }
 
 int64_t sparf_adam_workspace_floats(void) { return 256; }

@@ -103,6 +103,9 @@ EXPORTS = {
     "sparf_pose_compose_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sparf_pose_d9_forward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sparf_pose_d9_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sparf_reproj_workspace_bytes": (c_int64, [c_int]),
+    "sparf_reproj_loss": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_float, c_int, c_float] + [c_void_p] * 6),
+    "sparf_reproj_pair_loss": (c_int, [c_void_p] * 11 + [c_int, c_int, c_int, c_float, c_int, c_float] + [c_void_p] * 9),
     "sparf_adam_workspace_floats": (c_int64, []),
     "sparf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p]),

@@ -675,6 +675,132 @@ class D9Pose(torch.autograd.Function):
         return d_d9, None
 
 
+# ---------------------------------------------------------------------------------------------- correspondence loss
+REPROJ_LOSS_TYPES = {"huber": 0, "l1": 1, "mse": 2, "epe": 3}          # include/sparf_hip.h loss_type
+
+
+def _reproj_call(name, dev, n, head, opts, outs):
+    """one entry point of the correspondence loss on the current stream: the input pointers, n and the options, the
+    output pointers, the workspace (above the one-workgroup limit only) -- no host synchronisation, no readback"""
+    lib = L.load()
+    nb = int(lib.sparf_reproj_workspace_bytes(n))
+    ws = torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None
+    with L.on(dev):
+        L.check(getattr(lib, name)(*map(L.ptr, head), n, *opts, *map(L.ptr, outs), L.ptr(ws), L.stream_ptr(dev)), name)
+
+
+def _reproj_opts(loss_type, pixel_thresh, depth_thresh):
+    if loss_type.lower() not in REPROJ_LOSS_TYPES:
+        raise ValueError("Wrong loss type: {}".format(loss_type))
+    return (REPROJ_LOSS_TYPES[loss_type.lower()], int(pixel_thresh is not None), float(pixel_thresh or 0.0),
+            int(depth_thresh is not None), float(depth_thresh or 0.0))
+
+
+def _flat(t, n, what):
+    """[n] or [n,1] (or [1,n,1], as a render returns it) -> dense float32 [n]"""
+    if t.numel() != n:
+        raise ValueError(f"correspondence loss: {what} has {t.numel()} elements for {n} matches")
+    return _f32(t).reshape(n)
+
+
+def _pix(t):
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError("correspondence loss: pixels must be [n,2]")
+    return _f32(t)
+
+
+def _mat(t, shapes, what):
+    """a dense float32 copy of a matrix the kernels read whole: its shape is checked here, the library sees a pointer only"""
+    if tuple(t.shape) not in shapes:
+        raise ValueError(f"correspondence loss: {what} must be {' or '.join(str(list(x)) for x in shapes)}, got {list(t.shape)}")
+    return _f32(t)
+
+
+def _seed(s, like, g):
+    return (s * g).view(like) if s is not None else None
+
+
+class ReprojLoss(torch.autograd.Function):
+    """compute_render_and_repro_loss_w_repro_thres (corres_loss.py:50-95) for one direction i -> j: one library call for the loss, the
+    two stats, the valid mask and the gradient seeds of depth_i and T_itoj [4,4]; the backward multiplies the seeds by the upstream
+    scalar.  pixel_thresh / depth_thresh None: that check is off.  -> (loss, perc_val_pix_rep, perc_val_depth_rep, valid [n,1] | None)"""
+
+    @staticmethod
+    def forward(ctx, pixels_i, depth_i, intr_i, pixels_j, depth_j, intr_j, T_itoj, weights, loss_type, pixel_thresh, depth_thresh, want_valid):
+        dev = depth_i.device
+        L.require_gpu(dev)
+        opts = _reproj_opts(loss_type, pixel_thresh, depth_thresh)
+        pi, pj = _pix(pixels_i), _pix(pixels_j)
+        n = pi.shape[0]
+        if pj.shape[0] != n:
+            raise ValueError("correspondence loss: pixels_i and pixels_j must have one row per match")
+        K_i, K_j, T = _mat(intr_i, [(3, 3)], "intr_i"), _mat(intr_j, [(3, 3)], "intr_j"), _mat(T_itoj, [(4, 4)], "T_itoj")
+        di = _flat(depth_i, n, "depth_i")
+        dj = _flat(depth_j, n, "depth_j") if depth_j is not None else None
+        w = _flat(weights, n, "weights") if weights is not None else None
+        out = torch.empty(4, device=dev, dtype=torch.float32)
+        d_di = torch.empty(n, device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        d_T = torch.empty(4, 4, device=dev, dtype=torch.float32) if ctx.needs_input_grad[6] else None
+        valid = torch.empty(n, 1, device=dev, dtype=torch.bool) if want_valid else None
+        _reproj_call("sparf_reproj_loss", dev, n, (pi, di, K_i, pj, dj, K_j, T, w), opts, (out, d_di, d_T, valid))
+        ctx.save_for_backward(d_di, d_T)
+        ctx.depth_shape = depth_i.shape
+        loss, pix, dep, _ = out.unbind(0)
+        ctx.mark_non_differentiable(*(t for t in (pix, dep, valid) if t is not None))
+        return loss, pix, dep, valid
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        d_di, d_T = ctx.saved_tensors
+        return (None, _seed(d_di, ctx.depth_shape, g), None, None, None, None, _seed(d_T, (4, 4), g), None, None, None, None, None)
+
+
+class ReprojPairLoss(torch.autograd.Function):
+    """corres_loss.py:183-219 of compute_loss_on_image_pair for one view pair: both compositions of the relative pose, the two (four
+    with fine depths) re-projection terms, their mean and the stats in one library call, with the gradient seeds of every depth and of
+    both w2c poses [3,4].  -> (loss, perc_val_pix_rep, perc_val_depth_rep, depth_in_corr_loss)"""
+
+    @staticmethod
+    def forward(ctx, pixels_self, pixels_other, depth_self, depth_other, depth_fine_self, depth_fine_other, intr_self, intr_other,
+                pose_self, pose_other, weights, loss_type, pixel_thresh, depth_thresh):
+        dev = depth_self.device
+        L.require_gpu(dev)
+        opts = _reproj_opts(loss_type, pixel_thresh, depth_thresh)
+        if (depth_fine_self is None) != (depth_fine_other is None):
+            raise ValueError("correspondence loss: fine depths for one view only")
+        ps, po = _pix(pixels_self), _pix(pixels_other)
+        n = ps.shape[0]
+        if po.shape[0] != n:
+            raise ValueError("correspondence loss: pixels_self and pixels_other must have one row per match")
+        K = [_mat(t, [(3, 3)], "an intrinsics matrix") for t in (intr_self, intr_other)]
+        P = [_mat(t, [(3, 4), (4, 4)], "a w2c pose")[:3].contiguous() for t in (pose_self, pose_other)]
+        depths = [depth_self, depth_other, depth_fine_self, depth_fine_other]
+        d = [_flat(t, n, "a depth") if t is not None else None for t in depths]
+        w = _flat(weights, n, "weights") if weights is not None else None
+        out = torch.empty(4, device=dev, dtype=torch.float32)
+        seeds = [torch.empty(n, device=dev, dtype=torch.float32) if (t is not None and ctx.needs_input_grad[2 + i]) else None
+                 for i, t in enumerate(depths)]
+        d_pose = [torch.empty(3, 4, device=dev, dtype=torch.float32) if ctx.needs_input_grad[8 + i] else None for i in range(2)]
+        _reproj_call("sparf_reproj_pair_loss", dev, n, (ps, po, *d, *K, *P, w), opts, (out, *seeds, *d_pose))
+        ctx.save_for_backward(*seeds, *d_pose)
+        ctx.shapes = [t.shape if t is not None else None for t in depths] + [pose_self.shape, pose_other.shape]
+        loss, pix, dep, mean = out.unbind(0)
+        ctx.mark_non_differentiable(pix, dep, mean)
+        return loss, pix, dep, mean
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        saved = ctx.saved_tensors
+        grads = [_seed(s, shape, g) for s, shape in zip(saved[:4], ctx.shapes[:4])]
+        for s, shape in zip(saved[4:], ctx.shapes[4:]):
+            if s is not None and shape[-2] == 4:            # a [4,4] pose: its bottom row is a constant of the composition
+                s = torch.cat([s, torch.zeros_like(s[:1])])
+            grads.append(s * g if s is not None else None)
+        return (None, None, *grads[:4], None, None, *grads[4:], None, None, None, None)
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
 class Composite(torch.autograd.Function):
     """NeRF.composite (frequency_nerf.py:283-343) on caller-built per-sample values (C ABI 6 sparf_composite_forward / _backward):
