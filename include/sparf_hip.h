@@ -212,6 +212,74 @@ int sparf_reproj_pair_loss(const float* pixels_self, const float* pixels_other, 
                            float* d_depth_fine_self, float* d_depth_fine_other, float* d_pose_self, float* d_pose_other,
                            void* workspace /*NULL ok*/, void* stream);
 
+/* ---- depth-consistency loss ---------------------------------------------
+ * The body of DepthConsistencyLoss.compute_loss_at_sampled_pose
+ * (source/training/core/depth_cons_loss.py:219-321) around its two renders, as three calls;
+ * the renders, the pose sampler and the autograd graph stay the caller's.  All per-point
+ * arithmetic is double on the fp32 inputs, each stored value is rounded once, no call uses an
+ * atomic: two calls on the same inputs give the same bits.
+ * sparf_dcons_project replaces :247-259 and, in its back-projecting form, also :209.  Per point:
+ *   with points_w[n][3]: X_w = points_w;  otherwise (batch_backproject_to_3d,
+ *   source/utils/geometry/batched_geometry_utils.py:244-247)  x = K_ref^-1 [p, 1] d (closed-form
+ *   inverse of a general 3x3);  h = T_c2w [x, 1];  X_w = h[0:3] / (h[3] + 1e-6);
+ *   then (batch_project, :262-265)  g = P_unseen [X_w, 1];  X = g[0:3] / (g[3] + 1e-6);
+ *   y = K_unseen X;  uv = y[0:2] / (y[2] + 1e-6);  z = X[2].
+ *   Poses have ref_rows / unseen_rows = 3 or 4 rows of 4; a missing bottom row is [0,0,0,1].
+ *   The mask of :252-254 is decided on the values AS STORED (fp32):  uv.x >= 0, uv.y >= 0,
+ *   uv.x <= W-1, uv.y <= H-1, z >= depth_min; depth_min_dev (NULL ok) is the same value in
+ *   device memory and then depth_min is not read.
+ *   Outputs, an ordered compaction (the boolean indexing of :256-259 is stable): uv[count][2]
+ *   and z[count] of the surviving points in source order, dst[n] = output row of source point k
+ *   or -1, src[count] = source point of output row j, count[1] in device memory.  uv, z and src
+ *   need room for n rows.  Exactly one input form: points_w, or all of pixels_ref[n][2],
+ *   depth_ref[n], K_ref[3][3], pose_c2w_ref (the others NULL).
+ * sparf_dcons_project_backward: what autograd derives from those lines, as a gather over SOURCE
+ *   points through dst (no atomics, no zero-fill pass): from d_uv[count][2] and d_z[count]
+ *   (NULL ok each: zero) d_points_w[n][3] in the points form, d_depth_ref[n] in the
+ *   back-projecting form (the other NULL); zeros where dst < 0.  Nothing goes to K, the poses
+ *   or the reference pixels (:172 detaches the poses).
+ * sparf_dcons_select replaces :277-283: keep = vis >= thresh as an fp32 compare
+ *   (tensor.ge(0.2)), the same ordered compaction of uv[m][2], z[m] and vis[m], with dst, src
+ *   and count as above.  sparf_dcons_select_backward gathers d_uv / d_z (NULL ok each: zero)
+ *   through dst into d_uv_in[m][2] / d_z_in[m] (NULL ok each: skipped); vis gets no gradient.
+ * sparf_dcons_loss replaces :293-312 over the m kept points:  w = vis opacity (detached);
+ *   e = z_pseudo - depth;  l = huber_1(e) | |e| | e^2 for loss_type 0 huber, 1 l1, 2 mse
+ *   (compute_diff_loss, source/training/core/base_losses.py:197-224; `epe` is not a kernel
+ *   case: on a 1-D difference the reference's norm is that of the whole vector);
+ *   out[0] = sum l w / (m + 1e-6), plus the same term on depth_fine / opacity_fine when both
+ *   are given (NULL ok, together); out[1] = avg_vis_weight = sum w / (m + 1e-6) of the LAST
+ *   term (the reference overwrites the variable).  Seeds (NULL ok each) from the same launch:
+ *   d_z_pseudo[m], d_depth[m], d_depth_fine[m].  Sums are accumulated in double in a fixed
+ *   order.  The division by gamma (:315-319) stays the caller's.
+ * workspace: sparf_dcons_workspace_bytes(n) bytes for a call on n points (0 up to 4096 points:
+ *   one workgroup, one launch; above, per chunk of 4096 points a count or partial totals, two
+ *   launches; NULL = the one-workgroup path at any n).  n == 0 launches no kernel and looks at
+ *   no data pointer (an empty tensor has none); project and select then write count = 0, the
+ *   loss zeroes out.
+ * Each returns 1 before any HIP call for n < 0, an unknown loss_type, neither or both input
+ * forms (or a pose with other than 3 or 4 rows), fine depth without fine opacity (or the
+ * reverse, or a fine seed without fine depth), or a missing required pointer. */
+int64_t sparf_dcons_workspace_bytes(int n);
+int sparf_dcons_project(const float* points_w /*NULL ok*/, const float* pixels_ref /*NULL ok*/, const float* depth_ref /*NULL ok*/,
+                        const float* K_ref /*NULL ok*/, const float* pose_c2w_ref /*NULL ok*/, int ref_rows,
+                        const float* pose_w2c_unseen, int unseen_rows, const float* K_unseen, int n, int H, int W,
+                        float depth_min, const float* depth_min_dev /*NULL ok*/, float* uv, float* z, int32_t* dst, int32_t* src,
+                        int32_t* count, void* workspace /*NULL ok*/, void* stream);
+int sparf_dcons_project_backward(const float* points_w /*NULL ok*/, const float* pixels_ref /*NULL ok*/,
+                                 const float* depth_ref /*NULL ok*/, const float* K_ref /*NULL ok*/,
+                                 const float* pose_c2w_ref /*NULL ok*/, int ref_rows, const float* pose_w2c_unseen, int unseen_rows,
+                                 const float* K_unseen, int n, const int32_t* dst, const float* d_uv /*NULL ok*/,
+                                 const float* d_z /*NULL ok*/, float* d_points_w /*NULL ok*/, float* d_depth_ref /*NULL ok*/,
+                                 void* stream);
+int sparf_dcons_select(const float* vis, const float* uv, const float* z, int m, float thresh, float* uv_out, float* z_out,
+                       float* vis_out, int32_t* dst, int32_t* src, int32_t* count, void* workspace /*NULL ok*/, void* stream);
+int sparf_dcons_select_backward(const int32_t* dst, const float* d_uv /*NULL ok*/, const float* d_z /*NULL ok*/, int m,
+                                float* d_uv_in /*NULL ok*/, float* d_z_in /*NULL ok*/, void* stream);
+int sparf_dcons_loss(const float* z_pseudo, const float* vis, const float* depth, const float* opacity,
+                     const float* depth_fine /*NULL ok*/, const float* opacity_fine /*NULL ok*/, int m, int loss_type, float* out,
+                     float* d_z_pseudo /*NULL ok*/, float* d_depth /*NULL ok*/, float* d_depth_fine /*NULL ok*/,
+                     void* workspace /*NULL ok*/, void* stream);
+
 /* ---- optimiser step ----------------------------------------------------
  * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) (source/training/base.py:96-97,
  * engine after_backward; skipped when max_norm <= 0) followed by torch.optim.Adam.step()

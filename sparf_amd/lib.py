@@ -106,6 +106,12 @@ EXPORTS = {
     "sparf_reproj_workspace_bytes": (c_int64, [c_int]),
     "sparf_reproj_loss": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_float, c_int, c_float] + [c_void_p] * 6),
     "sparf_reproj_pair_loss": (c_int, [c_void_p] * 11 + [c_int, c_int, c_int, c_float, c_int, c_float] + [c_void_p] * 9),
+    "sparf_dcons_workspace_bytes": (c_int64, [c_int]),
+    "sparf_dcons_project": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float] + [c_void_p] * 8),
+    "sparf_dcons_project_backward": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 6),
+    "sparf_dcons_select": (c_int, [c_void_p] * 3 + [c_int, c_float] + [c_void_p] * 8),
+    "sparf_dcons_select_backward": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3),
+    "sparf_dcons_loss": (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 6),
     "sparf_adam_workspace_floats": (c_int64, []),
     "sparf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p]),

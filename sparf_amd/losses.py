@@ -1,4 +1,6 @@
-"""The correspondence loss: SPARF's re-projection of rendered depth at matched pixels through the current relative
+"""The correspondence loss and, below it, the depth-consistency loss.
+
+The correspondence loss: SPARF's re-projection of rendered depth at matched pixels through the current relative
 pose (corres_loss.py:50-95, :183-219; batched_geometry_utils.py:199-228; base_losses.py:197-224).
 
 The sampler, the renders and the autograd graph stay PyTorch's.  The BODY -- four re-projection terms and the two compositions of the
@@ -6,6 +8,12 @@ relative pose -- is one library call behind ops.ReprojLoss / ops.ReprojPairLoss 
 torch restatement of the same formulas, in this file, for everything else: CPU, float64, intrinsics / pixels / weights that require a
 gradient (the kernels give none to them), and `unfused()`.  `install()` puts the method under a trainer's own name.  Nothing in this
 package calls any of it; there is no `opt.hip` key.
+
+The depth-consistency loss (depth_cons_loss.py:219-321 compute_loss_at_sampled_pose; batched_geometry_utils.py:231-266) follows the same
+plan: its three renders stay the caller's, the chains between them are `depth_consistency_project` (ops.DconsProject), `visibility_select`
+(ops.DconsSelect) and `depth_consistency_loss` (ops.DconsLoss), each with a torch restatement here, and
+`install_depth_consistency()` puts the method under the reference's name.  The two masked selections become ordered compactions on the
+device; what is read back is the two ray counts the following renders need on the host.
 """
 import contextlib
 
@@ -213,6 +221,150 @@ def install(corres_loss_module):
 def uninstall():
     while _patched:
         obj, name, own, old = _patched.pop()
+        if own:
+            setattr(obj, name, old)
+        else:
+            delattr(obj, name)
+
+
+# ================================================================================================ the depth-consistency loss
+DCONS_LOSS_TYPES = tuple(ops.DCONS_LOSS_TYPES)
+
+
+# ---------------------------------------------------------------------------------------------- the torch restatement
+def backproject_to_3d_torch(kpi, di, Ki, T_itoj):
+    """batched_geometry_utils.py:231-248 batch_backproject_to_3d"""
+    x = _to_hom(kpi) @ torch.inverse(Ki).transpose(-1, -2) * di[..., None]
+    return _from_hom(_to_hom(x) @ T_itoj.transpose(-1, -2))
+
+
+def project_torch(points, T_itoj, Kj):
+    """batched_geometry_utils.py:251-266 batch_project with return_depth: -> (pixels [n,2], depth [n])"""
+    X = _from_hom(_to_hom(points) @ T_itoj.transpose(-1, -2))
+    return _from_hom(X @ Kj.transpose(-1, -2)), X[..., -1]
+
+
+def _index_of(mask):
+    return torch.nonzero(mask).reshape(-1).to(torch.int32)
+
+
+def depth_consistency_project_torch(points_w, pose_w2c_unseen, intr_unseen, H, W, depth_min, pixels_ref=None, depth_ref=None, intr_ref=None,
+                                    pose_c2w_ref=None):
+    """depth_cons_loss.py:209 (without points_w) and :247-259 -> (pixels [c,2], pseudo_depth [c], index [c])"""
+    if points_w is None:
+        dtype = depth_ref.dtype
+        points_w = backproject_to_3d_torch(pixels_ref.to(dtype), depth_ref.reshape(-1), intr_ref, _to_4x4(pose_c2w_ref))
+    uv, z = project_torch(points_w, _to_4x4(pose_w2c_unseen), intr_unseen)
+    valid = uv[:, 0].ge(0.) & uv[:, 1].ge(0.) & uv[:, 0].le(W - 1) & uv[:, 1].le(H - 1) & z.ge(depth_min)
+    return uv[valid], z[valid], _index_of(valid)
+
+
+def visibility_select_torch(vis, pixels, pseudo_depth, thresh=0.2):
+    """depth_cons_loss.py:277-283 -> (pixels [c,2], pseudo_depth [c], vis [c], index [c])"""
+    vis = vis.reshape(-1)
+    valid = vis.ge(thresh)
+    return pixels[valid], pseudo_depth.reshape(-1)[valid], vis[valid], _index_of(valid)
+
+
+def depth_consistency_loss_torch(pseudo_depth, vis, depth, opacity, depth_fine=None, opacity_fine=None, loss_type="huber"):
+    """depth_cons_loss.py:293-312 -> (loss, avg_vis_weight)"""
+    zp, v = pseudo_depth.reshape(-1), vis.detach().reshape(-1)
+    w = v * opacity.detach().reshape(-1)
+    loss = diff_loss_torch(loss_type, zp - depth.reshape(-1), weights=w)
+    if depth_fine is not None:
+        w = v * opacity_fine.detach().reshape(-1)
+        loss = loss + diff_loss_torch(loss_type, zp - depth_fine.reshape(-1), weights=w)
+    return loss, w.sum() / (w.nelement() + 1e-6)
+
+
+# ---------------------------------------------------------------------------------------------- the public functions
+def depth_consistency_project(points_w, pose_w2c_unseen, intr_unseen, H, W, depth_min, *, pixels_ref=None, depth_ref=None, intr_ref=None,
+                              pose_c2w_ref=None):
+    """Pseudo ground-truth points into an unseen view, and the ones that land in it: world points [n,3], or -- with points_w None --
+    pixels_ref [n,2] and depth_ref [n] of a reference view with intr_ref [3,3] and pose_c2w_ref ([3,4] or [4,4]), back-projected first.
+    pose_w2c_unseen [3,4] or [4,4], intr_unseen [3,3]; depth_min a float or a 0-dim tensor (depth_range[0][0]).  A point is kept if its
+    pixel lies in [0, W-1] x [0, H-1] and its depth is >= depth_min.  -> (pixels [c,2], pseudo_depth [c], index [c] int32) in source
+    order; index gathers whatever else the caller filters (pixels_in_ref[index]).  Gradients go to points_w / depth_ref only."""
+    back = (pixels_ref, depth_ref, intr_ref, pose_c2w_ref)
+    if any(t is None for t in back) if points_w is None else any(t is not None for t in back):      # one form, whole, on either route
+        raise ValueError("depth_consistency_project: either world points, or all of pixels_ref, depth_ref, intr_ref and pose_c2w_ref")
+    if isinstance(depth_min, torch.Tensor) and depth_min.device.type == "cpu":
+        depth_min = float(depth_min)                      # host memory: no synchronisation in reading it
+    dmin = depth_min if isinstance(depth_min, torch.Tensor) else None
+    if _takes_kernel((points_w, depth_ref), (pose_w2c_unseen, intr_unseen, pixels_ref, intr_ref, pose_c2w_ref, dmin)):
+        return ops.DconsProject.apply(points_w, pixels_ref, depth_ref, intr_ref, pose_c2w_ref, pose_w2c_unseen, intr_unseen, H, W, depth_min)
+    return depth_consistency_project_torch(points_w, pose_w2c_unseen, intr_unseen, H, W, depth_min, pixels_ref, depth_ref, intr_ref, pose_c2w_ref)
+
+
+def visibility_select(vis, pixels, pseudo_depth, thresh=0.2):
+    """The visibility threshold: the rows with vis >= thresh of pixels [m,2], pseudo_depth [m] and vis [m] (or [m,1]), in order.
+    -> (pixels [c,2], pseudo_depth [c], vis [c], index [c] int32).  vis gets no gradient."""
+    if _takes_kernel((pixels, pseudo_depth), (vis,)):
+        return ops.DconsSelect.apply(vis, pixels, pseudo_depth, thresh)
+    return visibility_select_torch(vis, pixels, pseudo_depth, thresh)
+
+
+def depth_consistency_loss(pseudo_depth, vis, depth, opacity, depth_fine=None, opacity_fine=None, loss_type="huber"):
+    """The weighted difference of the pseudo depth and the rendered depth over the m kept points: w = vis opacity (both detached),
+    loss = sum l(pseudo_depth - depth) w / (m + 1e-6), plus the same on depth_fine / opacity_fine when given.
+    -> (loss, avg_vis_weight = sum w / (m + 1e-6) of the last term)."""
+    if (depth_fine is None) != (opacity_fine is None):
+        raise ValueError("depth_consistency_loss: depth_fine and opacity_fine come together")
+    if loss_type.lower() not in DCONS_LOSS_TYPES + ("epe",):
+        raise ValueError("Wrong loss type: {}".format(loss_type))
+    if loss_type.lower() != "epe" and _takes_kernel((pseudo_depth, depth, depth_fine), (vis.detach(), opacity.detach(),
+                                                                                        opacity_fine.detach() if opacity_fine is not None else None)):
+        return ops.DconsLoss.apply(pseudo_depth, vis, depth, opacity, depth_fine, opacity_fine, loss_type)
+    return depth_consistency_loss_torch(pseudo_depth, vis, depth, opacity, depth_fine, opacity_fine, loss_type)
+
+
+def compute_loss_at_sampled_pose(self, data_dict, pose_w2c_at_unseen, intr_at_unseen, pseudo_gt_3dpts_in_w, H, W, pixels_in_ref):
+    """The method of DepthConsistencyLoss (depth_cons_loss.py:219-321) under its own signature and return convention: reads
+    self.opt.diff_loss_type, gradually_decrease_depth_cons_loss and depth_cons_loss_reduct_at_x_iter, calls self.net's two render
+    methods as :267 and :291 do.  (The reference also filters pixels_in_ref and the world points and never reads them again; its
+    assert on the visibility, a host synchronisation, is left out.)"""
+    iteration = data_dict['iter']
+    stats_dict, plotting_dict = {'nbr_px_sampling': pseudo_gt_3dpts_in_w.shape[0]}, {}
+    empty = lambda: ({'depth_cons': torch.tensor(0., requires_grad=True).to(self.device)}, {}, {})
+    pixels, pseudo_depth, _ = depth_consistency_project(pseudo_gt_3dpts_in_w, pose_w2c_at_unseen, intr_at_unseen, H, W,
+                                                        data_dict.depth_range[0][0])
+    if pseudo_depth.shape[0] == 0:
+        return empty()
+    with torch.no_grad():
+        ret_max = self.net.render_up_to_maxdepth_at_specific_pose_and_rays(self.opt, data_dict, pose_w2c_at_unseen[:3], intr_at_unseen, H, W,
+                                                                           depth_max=pseudo_depth, pixels=pixels, mode='train', iter=iteration)
+        vis = ret_max['all_cumulated_fine'] if 'all_cumulated_fine' in ret_max.keys() else ret_max['all_cumulated']
+    pixels, pseudo_depth, vis, _ = visibility_select(vis.squeeze(0), pixels, pseudo_depth, 0.2)
+    if pseudo_depth.shape[0] == 0:
+        return empty()
+    ret = self.net.render_image_at_specific_pose_and_rays(self.opt, data_dict, pose_w2c_at_unseen[:3], intr_at_unseen, H, W, pixels=pixels,
+                                                          mode='train', iter=iteration)
+    fine = 'rgb_fine' in ret.keys()
+    loss, avg = depth_consistency_loss(pseudo_depth, vis, ret.depth, ret.opacity, ret.depth_fine if fine else None,
+                                       ret.opacity_fine if fine else None, loss_type=self.opt.diff_loss_type)
+    stats_dict['avg_vis_weight'] = avg
+    if self.opt.gradually_decrease_depth_cons_loss:
+        loss = loss / 2 ** (iteration // self.opt.depth_cons_loss_reduct_at_x_iter)
+    return {'depth_cons': loss}, stats_dict, plotting_dict
+
+
+DCONS_METHOD = "compute_loss_at_sampled_pose"
+_patched_dcons = []
+
+
+def install_depth_consistency(depth_cons_loss_module):
+    """Opt-in, and independent of install(): put the method above on `depth_cons_loss_module.DepthConsistencyLoss` until
+    `uninstall_depth_consistency()`.  Nothing in this package calls it."""
+    if _patched_dcons:
+        raise RuntimeError("sparf_amd.losses.install_depth_consistency: already installed; call uninstall_depth_consistency() first")
+    cls = depth_cons_loss_module.DepthConsistencyLoss
+    _patched_dcons.append((cls, DCONS_METHOD, DCONS_METHOD in vars(cls), vars(cls).get(DCONS_METHOD)))
+    setattr(cls, DCONS_METHOD, compute_loss_at_sampled_pose)
+
+
+def uninstall_depth_consistency():
+    while _patched_dcons:
+        obj, name, own, old = _patched_dcons.pop()
         if own:
             setattr(obj, name, old)
         else:

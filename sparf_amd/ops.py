@@ -696,23 +696,23 @@ def _reproj_opts(loss_type, pixel_thresh, depth_thresh):
             int(depth_thresh is not None), float(depth_thresh or 0.0))
 
 
-def _flat(t, n, what):
-    """[n] or [n,1] (or [1,n,1], as a render returns it) -> dense float32 [n]"""
+def _flat(t, n, what, op="correspondence loss", rows="matches"):
+    """[n] or [n,1] (or [1,n,1], as a render returns it) -> dense float32 [n]; `op` and `rows` name the caller in the message"""
     if t.numel() != n:
-        raise ValueError(f"correspondence loss: {what} has {t.numel()} elements for {n} matches")
+        raise ValueError(f"{op}: {what} has {t.numel()} elements for {n} {rows}")
     return _f32(t).reshape(n)
 
 
-def _pix(t):
+def _pix(t, op="correspondence loss"):
     if t.dim() != 2 or t.shape[1] != 2:
-        raise ValueError("correspondence loss: pixels must be [n,2]")
+        raise ValueError(f"{op}: pixels must be [n,2]")
     return _f32(t)
 
 
-def _mat(t, shapes, what):
+def _mat(t, shapes, what, op="correspondence loss"):
     """a dense float32 copy of a matrix the kernels read whole: its shape is checked here, the library sees a pointer only"""
     if tuple(t.shape) not in shapes:
-        raise ValueError(f"correspondence loss: {what} must be {' or '.join(str(list(x)) for x in shapes)}, got {list(t.shape)}")
+        raise ValueError(f"{op}: {what} must be {' or '.join(str(list(x)) for x in shapes)}, got {list(t.shape)}")
     return _f32(t)
 
 
@@ -799,6 +799,172 @@ class ReprojPairLoss(torch.autograd.Function):
                 s = torch.cat([s, torch.zeros_like(s[:1])])
             grads.append(s * g if s is not None else None)
         return (None, None, *grads[:4], None, None, *grads[4:], None, None, None, None)
+
+
+# ---------------------------------------------------------------------------------------------- depth-consistency loss
+DCONS_LOSS_TYPES = {"huber": 0, "l1": 1, "mse": 2}          # include/sparf_hip.h: `epe` is not a kernel case
+
+
+def _dcons_call(name, dev, *args, ws_for=None):
+    """one entry point of the depth-consistency loss on the current stream; `ws_for`: the number of points of a call
+    that takes a workspace (above the one-workgroup limit only)"""
+    lib = L.load()
+    tail = ()
+    if ws_for is not None:
+        nb = int(lib.sparf_dcons_workspace_bytes(ws_for))
+        tail = (L.ptr(torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None),)
+    with L.on(dev):
+        L.check(getattr(lib, name)(*args, *tail, L.stream_ptr(dev)), name)
+
+
+def _dcons_compacted(dev, n):
+    """dst [n], src [room for n], count [1]: the index tensors of an ordered compaction"""
+    i32 = lambda k: torch.empty(k, device=dev, dtype=torch.int32)
+    return i32(n), i32(n), i32(1)
+
+
+def _dcons_count(count, n):
+    """the one readback of a compaction: 4 bytes, the number of rays of the render that follows"""
+    return int(count.item()) if n else 0
+
+
+def _pose_rows(t, what, op):
+    m = _mat(t, [(3, 4), (4, 4)], what, op)
+    return m, m.shape[0]
+
+
+class DconsProject(torch.autograd.Function):
+    """depth_cons_loss.py:247-259 (with `points_w` None also :209, batch_backproject_to_3d of pixels_ref [n,2] and depth_ref through
+    intr_ref and pose_c2w_ref): batch_project into the unseen view, the five-way mask on the stored values and its selections as one
+    ordered compaction.  depth_min: a float or a float32 scalar on the device (then it is never read back).
+    -> (pixels [c,2], pseudo_depth [c], index [c] int32: the source row of each output row).  Gradients go to points_w or depth_ref."""
+
+    @staticmethod
+    def forward(ctx, points_w, pixels_ref, depth_ref, intr_ref, pose_c2w_ref, pose_w2c_unseen, intr_unseen, H, W, depth_min):
+        dev = pose_w2c_unseen.device
+        L.require_gpu(dev)
+        op = "depth-consistency project"
+        P, prows = _pose_rows(pose_w2c_unseen, "pose_w2c_unseen", op)
+        K = _mat(intr_unseen, [(3, 3)], "intr_unseen", op)
+        if points_w is not None:
+            if any(t is not None for t in (pixels_ref, depth_ref, intr_ref, pose_c2w_ref)):
+                raise ValueError("depth-consistency project: world points or a back-projection, not both")
+            if points_w.dim() != 2 or points_w.shape[1] != 3:
+                raise ValueError("depth-consistency project: points_w must be [n,3]")
+            head, rrows = (_f32(points_w), None, None, None, None), 0
+            n = head[0].shape[0]
+        else:
+            if any(t is None for t in (pixels_ref, depth_ref, intr_ref, pose_c2w_ref)):
+                raise ValueError("depth-consistency project: the back-projection needs pixels_ref, depth_ref, intr_ref and pose_c2w_ref")
+            px = _pix(pixels_ref, op)
+            n = px.shape[0]
+            T, rrows = _pose_rows(pose_c2w_ref, "pose_c2w_ref", op)
+            head = (None, px, _flat(depth_ref, n, "depth_ref", op, "points"), _mat(intr_ref, [(3, 3)], "intr_ref", op), T)
+        dmin_dev = None
+        if isinstance(depth_min, torch.Tensor):
+            dmin_dev, depth_min = _f32(depth_min).reshape(1), 0.0
+        uv = torch.empty(n, 2, device=dev, dtype=torch.float32)
+        z = torch.empty(n, device=dev, dtype=torch.float32)
+        dst, src, count = _dcons_compacted(dev, n)
+        p = L.ptr
+        _dcons_call("sparf_dcons_project", dev, *map(p, head), rrows, p(P), prows, p(K), n, int(H), int(W), float(depth_min), p(dmin_dev),
+                    p(uv), p(z), p(dst), p(src), p(count), ws_for=n)
+        c = _dcons_count(count, n)
+        ctx.save_for_backward(*head, P, K, dst)
+        ctx.rows, ctx.shape = (rrows, prows), (points_w if points_w is not None else depth_ref).shape
+        ctx.set_materialize_grads(False)
+        index = src[:c]
+        ctx.mark_non_differentiable(index)
+        return uv[:c], z[:c], index
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_uv, g_z, _):
+        *head, P, K, dst = ctx.saved_tensors
+        if (g_uv is None and g_z is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
+            return (None,) * 10
+        dev, n, by_points = dst.device, dst.shape[0], head[0] is not None
+        out = torch.empty((n, 3) if by_points else (n,), device=dev, dtype=torch.float32)
+        p = L.ptr
+        _dcons_call("sparf_dcons_project_backward", dev, *map(p, head), ctx.rows[0], p(P), ctx.rows[1], p(K), n, p(dst),
+                    p(_f32(g_uv) if g_uv is not None else None), p(_f32(g_z) if g_z is not None else None),
+                    p(out if by_points else None), p(None if by_points else out))
+        out = out.view(ctx.shape)
+        return (out if by_points else None, None, None if by_points else out) + (None,) * 7
+
+
+class DconsSelect(torch.autograd.Function):
+    """depth_cons_loss.py:277-283: keep = vis >= thresh (an fp32 compare) and the same ordered compaction of pixels [m,2], pseudo_depth
+    [m] and vis [m].  -> (pixels [c,2], pseudo_depth [c], vis [c], index [c] int32).  Gradients go to pixels and pseudo_depth."""
+
+    @staticmethod
+    def forward(ctx, vis, pixels, pseudo_depth, thresh):
+        dev = vis.device
+        L.require_gpu(dev)
+        op = "visibility select"
+        uv = _pix(pixels, op)
+        m = uv.shape[0]
+        v, z = _flat(vis, m, "vis", op, "points"), _flat(pseudo_depth, m, "pseudo_depth", op, "points")
+        uv_o, z_o, v_o = torch.empty_like(uv), torch.empty_like(z), torch.empty_like(v)
+        dst, src, count = _dcons_compacted(dev, m)
+        p = L.ptr
+        _dcons_call("sparf_dcons_select", dev, p(v), p(uv), p(z), m, float(thresh), p(uv_o), p(z_o), p(v_o), p(dst), p(src), p(count), ws_for=m)
+        c = _dcons_count(count, m)
+        ctx.save_for_backward(dst)
+        ctx.shapes = (pixels.shape, pseudo_depth.shape)
+        ctx.set_materialize_grads(False)
+        vis_out, index = v_o[:c], src[:c]
+        ctx.mark_non_differentiable(vis_out, index)
+        return uv_o[:c], z_o[:c], vis_out, index
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_uv, g_z, *_):
+        dst, = ctx.saved_tensors
+        need_uv, need_z = ctx.needs_input_grad[1] and g_uv is not None, ctx.needs_input_grad[2] and g_z is not None
+        if not (need_uv or need_z):
+            return None, None, None, None
+        dev, m = dst.device, dst.shape[0]
+        d_uv = torch.empty(m, 2, device=dev, dtype=torch.float32) if need_uv else None
+        d_z = torch.empty(m, device=dev, dtype=torch.float32) if need_z else None
+        p = L.ptr
+        _dcons_call("sparf_dcons_select_backward", dev, p(dst), p(_f32(g_uv) if need_uv else None), p(_f32(g_z) if need_z else None), m, p(d_uv),
+                    p(d_z))
+        return None, d_uv.view(ctx.shapes[0]) if need_uv else None, d_z.view(ctx.shapes[1]) if need_z else None, None
+
+
+class DconsLoss(torch.autograd.Function):
+    """depth_cons_loss.py:293-312 over the m kept points: w = vis opacity (detached), l = compute_diff_loss(pseudo_depth - depth) with
+    weights w, the same on depth_fine / opacity_fine when given, avg_vis_weight of the last term -- one library call that also leaves the
+    gradient seeds of pseudo_depth, depth and depth_fine; the backward multiplies them by the upstream scalar.  -> (loss, avg_vis_weight)"""
+
+    @staticmethod
+    def forward(ctx, pseudo_depth, vis, depth, opacity, depth_fine, opacity_fine, loss_type):
+        dev = depth.device
+        L.require_gpu(dev)
+        if loss_type.lower() not in DCONS_LOSS_TYPES:
+            raise ValueError("Wrong loss type: {}".format(loss_type))
+        if (depth_fine is None) != (opacity_fine is None):
+            raise ValueError("depth-consistency loss: depth_fine and opacity_fine come together")
+        m = pseudo_depth.numel()
+        tensors = (pseudo_depth, vis, depth, opacity, depth_fine, opacity_fine)
+        names = ("pseudo_depth", "vis", "depth", "opacity", "depth_fine", "opacity_fine")
+        head = [_flat(t, m, name, "depth-consistency loss", "points") if t is not None else None for t, name in zip(tensors, names)]
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+        seeds = [torch.empty(m, device=dev, dtype=torch.float32) if (tensors[i] is not None and ctx.needs_input_grad[i]) else None for i in (0, 2, 4)]
+        p = L.ptr
+        _dcons_call("sparf_dcons_loss", dev, *map(p, head), m, DCONS_LOSS_TYPES[loss_type.lower()], p(out), *map(p, seeds), ws_for=m)
+        ctx.save_for_backward(*seeds)
+        ctx.shapes = [tensors[i].shape if tensors[i] is not None else None for i in (0, 2, 4)]
+        loss, avg = out.unbind(0)
+        ctx.mark_non_differentiable(avg)
+        return loss, avg
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        d_zp, d_depth, d_fine = (_seed(s, shape, g) for s, shape in zip(ctx.saved_tensors, ctx.shapes))
+        return d_zp, None, d_depth, None, d_fine, None, None
 
 
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
