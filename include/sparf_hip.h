@@ -280,6 +280,52 @@ int sparf_dcons_loss(const float* z_pseudo, const float* vis, const float* depth
                      float* d_z_pseudo /*NULL ok*/, float* d_depth /*NULL ok*/, float* d_depth_fine /*NULL ok*/,
                      void* workspace /*NULL ok*/, void* stream);
 
+/* ---- photometric, mask and depth-patch loss --------------------------------
+ * BasePhotoandReguLoss.compute_loss (source/training/core/base_losses.py:243-323, with the
+ * depth-patch regulariser of :180-194 and regularization_losses.py:51-66) and compute_mse_on_rays
+ * (source/training/core/metrics.py:33-75) as ONE call on rows = B N rendered rays: it gathers the
+ * ground-truth colours and the mask in place and writes every loss term, the two logged MSEs and
+ * the gradient seeds.  The distortion loss is not part of it.  Arithmetic as above: double on the
+ * fp32 operands, sums in double in a fixed order, one rounding per stored value, no atomic.
+ * Gather: the target of ray r of image b, channel c, is image[b][c][idx] (channel-planar, as
+ *   data_dict.image is stored) and its mask value fg_mask[b][idx] (bytes 0 / 1: torch.bool
+ *   storage), with idx = ray_idx[r] (per_image = 0, one list for all images), ray_idx[b][r]
+ *   (per_image = 1) or r itself (ray_idx NULL: full images, N = HW).  Indices may repeat; they lie
+ *   in [0, HW) (one outside is clamped, so that the launch stays inside the image).
+ * Per element, with e = pred - target:  kind 0 (MSE_loss, :151-153)  l = e^2;  kind 1
+ *   (torch.nn.functional.huber_loss with delta; the module's huber_loss, :155-156, is delta 0.5)
+ *   l = 0.5 e^2 if |e| <= delta else delta (|e| - 0.5 delta).
+ * Mask (:313-319):  l = |fg - opacity|, derivative -sgn(fg - opacity) with sgn(0) = 0.
+ * Depth patch: for every P^2 consecutive rays d_0 .. d_{M-1} of an image (M = P^2, N % M == 0)
+ *   l = sum_i sum_j sqrt((d_i - d_j)^2 + charbonnier^2) over all M^2 ordered pairs, diagonal
+ *   included;  d l / d d_i = 2 sum_j (d_i - d_j) / sqrt((d_i - d_j)^2 + charbonnier^2).
+ * out[0] render      kind 0: sum e^2 / (3 rows + 1e-6);  kind 1: 2 sum l / (3 rows);  plus the same
+ *                    on rgb_fine when given (:303-311)
+ * out[1] fg_mask     0.5 sum |fg - opacity| / rows, plus the same on opacity_fine; 0 without fg_mask
+ * out[2] depth_patch 0.02 sum over patches of l / (rows P^2), plus the same on depth_fine; 0 with
+ *                    patch = 0
+ * out[3], out[4]     mse, mse_fine: sum e^2 / (3 rows) on rgb and rgb_fine (metrics.py:26-31),
+ *                    whatever `kind` is; out[4] = 0 without rgb_fine
+ * Seeds (NULL ok each: not computed) from the same launch, each the derivative of ITS OWN out[k]:
+ *   d_rgb, d_rgb_fine [rows][3] of out[0]; d_opacity, d_opacity_fine [rows] of out[1]; d_depth,
+ *   d_depth_fine [rows] of out[2] (zeros when that term is off).  The caller multiplies each by the
+ *   upstream scalar of its loss.
+ * workspace: sparf_photo_regu_workspace_bytes(rows) bytes (0 up to 4096 rows: one workgroup, one
+ *   launch; above, partial totals per chunk of 4096 rows and a second launch that adds them in
+ *   chunk order; NULL = the one-workgroup path at any size).  A row sums over its own patch, so no
+ *   patch is split between workgroups.  rows == 0 launches nothing and zeroes out.
+ * Returns 1 before any HIP call for a negative size, kind outside {0, 1}, patch < 0 or > 8,
+ * patch > 0 with N % P^2 != 0 or without depth, a seed without its tensor, fg_mask without
+ * opacity, ray_idx NULL with N != HW, or a missing required pointer (image, rgb, out). */
+int64_t sparf_photo_regu_workspace_bytes(int64_t rows);
+int sparf_photo_regu_loss(const float* image, const unsigned char* fg_mask /*NULL ok*/, const int64_t* ray_idx /*NULL ok*/,
+                          int per_image, int B, int HW, int N, const float* rgb, const float* rgb_fine /*NULL ok*/,
+                          const float* opacity /*NULL ok*/, const float* opacity_fine /*NULL ok*/, const float* depth /*NULL ok*/,
+                          const float* depth_fine /*NULL ok*/, int kind, float delta, int patch, float charbonnier, float* out,
+                          float* d_rgb /*NULL ok*/, float* d_rgb_fine /*NULL ok*/, float* d_opacity /*NULL ok*/,
+                          float* d_opacity_fine /*NULL ok*/, float* d_depth /*NULL ok*/, float* d_depth_fine /*NULL ok*/,
+                          void* workspace /*NULL ok*/, void* stream);
+
 /* ---- optimiser step ----------------------------------------------------
  * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) (source/training/base.py:96-97,
  * engine after_backward; skipped when max_norm <= 0) followed by torch.optim.Adam.step()

@@ -112,6 +112,8 @@ EXPORTS = {
     "sparf_dcons_select": (c_int, [c_void_p] * 3 + [c_int, c_float] + [c_void_p] * 8),
     "sparf_dcons_select_backward": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3),
     "sparf_dcons_loss": (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 6),
+    "sparf_photo_regu_workspace_bytes": (c_int64, [c_int64]),
+    "sparf_photo_regu_loss": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 6 + [c_int, c_float, c_int, c_float] + [c_void_p] * 9),
     "sparf_adam_workspace_floats": (c_int64, []),
     "sparf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p]),

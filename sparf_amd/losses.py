@@ -1,4 +1,5 @@
-"""The correspondence loss and, below it, the depth-consistency loss.
+"""The correspondence loss and, below it, the depth-consistency loss and the photometric, mask and
+depth-patch loss.
 
 The correspondence loss: SPARF's re-projection of rendered depth at matched pixels through the current relative
 pose (corres_loss.py:50-95, :183-219; batched_geometry_utils.py:199-228; base_losses.py:197-224).
@@ -14,6 +15,10 @@ plan: its three renders stay the caller's, the chains between them are `depth_co
 (ops.DconsSelect) and `depth_consistency_loss` (ops.DconsLoss), each with a torch restatement here, and
 `install_depth_consistency()` puts the method under the reference's name.  The two masked selections become ordered compactions on the
 device; what is read back is the two ray counts the following renders need on the host.
+
+The photometric, mask and depth-patch loss (base_losses.py:243-323, :180-194; metrics.py:33-75) is ONE call, `photo_and_regu_loss`
+(ops.PhotoReguLoss), that gathers the ground-truth pixels in the kernel; `mse_on_rays` is the same call without seeds, and
+`install_photometric()` puts the method and, if asked, the metric under the reference's names.  It reads nothing back.
 """
 import contextlib
 
@@ -369,3 +374,210 @@ def uninstall_depth_consistency():
             setattr(obj, name, old)
         else:
             delattr(obj, name)
+
+
+# ================================================================================================ the photometric, mask and depth-patch loss
+# BasePhotoandReguLoss.compute_loss (base_losses.py:243-323 with compute_regularization_losses' depth-patch term,
+# :180-194, regularization_losses.py:51-66) and compute_mse_on_rays (metrics.py:33-75), the loss module every trainer runs on every
+# iteration.  One library call (ops.PhotoReguLoss) gathers the ground-truth colours and the mask in place and leaves every term, the two
+# logged MSEs and the gradient seeds; the torch restatement below serves everything else.  The distortion loss is not part of it: a config
+# with loss_weight.distortion set is handed to the original method.
+PHOTO_METHOD = "compute_loss"
+MSE_NAME = "compute_mse_on_rays"
+
+
+# ---------------------------------------------------------------------------------------------- the torch restatement
+def gather_rays_torch(per_pixel, ray_idx):
+    """base_losses.py:285-301 and metrics.py:58-68 on a [B, H*W, C] tensor: -> [B, N, C] (None: the whole images)"""
+    if ray_idx is None:
+        return per_pixel
+    B = per_pixel.shape[0]
+    if len(ray_idx.shape) == 2 and ray_idx.shape[0] == B:
+        n_rays = ray_idx.shape[-1]
+        batch_idx_flattened = torch.arange(start=0, end=B).unsqueeze(-1).repeat(1, n_rays).long().view(-1)
+        return per_pixel[batch_idx_flattened, ray_idx.reshape(-1).long()].reshape(B, n_rays, -1)
+    return per_pixel[:, ray_idx]
+
+
+def colour_loss_torch(pred, label, huber):
+    """base_losses.py:151-156 MSE_loss / huber_loss"""
+    if huber:
+        return torch.nn.functional.huber_loss(pred, label, reduction="mean", delta=ops.PHOTO_HUBER_DELTA) * 2.
+    loss = (pred.contiguous() - label) ** 2
+    return loss.sum() / (loss.nelement() + 1e-6)
+
+
+def fg_mask_loss_torch(fg, opacity):
+    """base_losses.py:315-316 on the gathered mask [B,N,1] (float) and opacity [B,N,1]"""
+    return 0.5 * torch.abs(fg - opacity).mean()
+
+
+def depth_patch_loss_torch(depths, patch_size, charbonnier=0.001):
+    """regularization_losses.py:51-66 depth_patch_loss on [B, N(, 1)] depths, times base_losses.py:182's strength"""
+    B = depths.shape[0]
+    depths = depths.reshape(B, -1, patch_size ** 2)
+    resid_sq = (depths[..., None] - depths[..., None, :]) ** 2
+    return 0.02 * torch.sqrt(resid_sq + charbonnier ** 2).mean()
+
+
+def _mse_torch(pred, label):
+    """metrics.py:26-31 MSE_loss without a mask"""
+    return ((pred.contiguous() - label) ** 2).mean()
+
+
+def photo_and_regu_loss_torch(image, ray_idx, rgb, rgb_fine=None, *, fg_mask=None, opacity=None, opacity_fine=None, depth=None, depth_fine=None,
+                              huber=False, patch_size=None, charbonnier=0.001):
+    """base_losses.py:274-319 and :180-194 in the reference's operation order -> (dict of the terms that are on, dict(mse, mse_fine))"""
+    B = image.shape[0]
+    target = gather_rays_torch(image.reshape(B, 3, -1).permute(0, 2, 1), ray_idx)
+    loss = dict(render=colour_loss_torch(rgb.reshape(B, -1, 3), target, huber))
+    mse = dict(mse=_mse_torch(rgb.detach().reshape(B, -1, 3), target.detach()), mse_fine=None)
+    if rgb_fine is not None:
+        loss["render"] = loss["render"] + colour_loss_torch(rgb_fine.reshape(B, -1, 3), target, huber)
+        mse["mse_fine"] = _mse_torch(rgb_fine.detach().reshape(B, -1, 3), target.detach())
+    if fg_mask is not None:
+        fg = gather_rays_torch(fg_mask.float().view(B, -1, 1), ray_idx)
+        loss["fg_mask"] = fg_mask_loss_torch(fg, opacity.reshape(B, -1, 1))
+        if opacity_fine is not None:
+            loss["fg_mask"] = loss["fg_mask"] + fg_mask_loss_torch(fg, opacity_fine.reshape(B, -1, 1))
+    if patch_size is not None:
+        loss["depth_patch"] = depth_patch_loss_torch(depth.reshape(B, -1), patch_size, charbonnier)
+        if depth_fine is not None:
+            loss["depth_patch"] = loss["depth_patch"] + depth_patch_loss_torch(depth_fine.reshape(B, -1), patch_size, charbonnier)
+    return loss, mse
+
+
+def _rendered_images(image, idx_img_rendered):
+    """metrics.py:52-56 image[idx_img_rendered]; a host-side index that names every image in order selects nothing and copies nothing"""
+    B = image.shape[0]
+    if not (isinstance(idx_img_rendered, torch.Tensor) and idx_img_rendered.device.type != "cpu"):
+        if [int(i) for i in idx_img_rendered] == list(range(B)):
+            return image
+    return image[idx_img_rendered]
+
+
+def mse_on_rays_torch(data_dict, output_dict):
+    """metrics.py:33-75 compute_mse_on_rays -> (mse_coarse, mse_fine or None)"""
+    batch_size = len(data_dict.idx)
+    image = data_dict.image.reshape(batch_size, 3, -1).permute(0, 2, 1)
+    nbr = len(output_dict.idx_img_rendered)
+    image = gather_rays_torch(image[output_dict.idx_img_rendered].reshape(nbr, -1, 3), output_dict.ray_idx if 'ray_idx' in output_dict.keys() else None)
+    mse_fine = None
+    if 'rgb_fine' in output_dict.keys():
+        mse_fine = _mse_torch(output_dict.rgb_fine.reshape(nbr, -1, 3), image)
+    return _mse_torch(output_dict.rgb.reshape(nbr, -1, 3), image), mse_fine
+
+
+# ---------------------------------------------------------------------------------------------- the public functions
+def _photo_takes_kernel(image, ray_idx, fg_mask, values, patch_size):
+    return (_takes_kernel(values, (image, ray_idx, fg_mask)) and image.dtype == torch.float32 and
+            (ray_idx is None or ray_idx.dtype == torch.int64) and (fg_mask is None or fg_mask.dtype == torch.bool) and
+            (patch_size is None or 0 < patch_size <= ops.PHOTO_MAX_PATCH))
+
+
+def photo_and_regu_loss(image, ray_idx, rgb, rgb_fine=None, *, fg_mask=None, opacity=None, opacity_fine=None, depth=None, depth_fine=None,
+                        huber=False, patch_size=None, charbonnier=0.001):
+    """The photometric loss of rendered rays against image [B,3,H,W] with, if asked for, the foreground-mask loss and the depth-patch
+    regulariser: rgb / rgb_fine [B,N,3]; ray_idx int64 [N] (the same rays of every image), [B,N] (per image) or None (full images,
+    N = H W); fg_mask (torch.bool, one element per pixel) switches the mask term on and needs opacity [B,N,1]; patch_size = P switches
+    the depth-patch term on and needs depth [B,N,1] with N a multiple of P^2; a fine tensor adds the same term on the fine head.
+    huber: the module's Huber loss (delta 0.5, x 2) in place of the MSE.
+    -> (dict(render, fg_mask, depth_patch) with the terms that are on, dict(mse, mse_fine: None without rgb_fine)): 0-dim tensors; the
+    mse values carry no gradient.  Gradients go to the six rendered tensors, none to the image."""
+    if fg_mask is not None and opacity is None:
+        raise ValueError("photo_and_regu_loss: the mask term needs opacity")
+    if patch_size is not None and depth is None:
+        raise ValueError("photo_and_regu_loss: the depth-patch term needs depth")
+    on = lambda t, used: t if used else None
+    values = (rgb, rgb_fine, on(opacity, fg_mask is not None), on(opacity_fine, fg_mask is not None), on(depth, patch_size is not None),
+              on(depth_fine, patch_size is not None))
+    if _photo_takes_kernel(image, ray_idx, fg_mask, values, patch_size):
+        render, mask, dpatch, mse, mse_fine = ops.PhotoReguLoss.apply(image, fg_mask, ray_idx, *values, "huber" if huber else "mse",
+                                                                      ops.PHOTO_HUBER_DELTA, patch_size or 0, charbonnier)
+        loss = dict(render=render)
+        if fg_mask is not None:
+            loss["fg_mask"] = mask
+        if patch_size is not None:
+            loss["depth_patch"] = dpatch
+        return loss, dict(mse=mse, mse_fine=mse_fine if rgb_fine is not None else None)
+    return photo_and_regu_loss_torch(image, ray_idx, rgb, rgb_fine, fg_mask=fg_mask, opacity=opacity, opacity_fine=opacity_fine, depth=depth,
+                                     depth_fine=depth_fine, huber=huber, patch_size=patch_size, charbonnier=charbonnier)
+
+
+def mse_on_rays(data_dict, output_dict):
+    """compute_mse_on_rays (metrics.py:33-75) under its own signature and return convention, indexing by idx_img_rendered included:
+    the same kernel with no seeds and no other term.  -> (mse_coarse, mse_fine or None)"""
+    ray_idx = output_dict.ray_idx if 'ray_idx' in output_dict.keys() else None
+    rgb = output_dict.rgb.detach()
+    rgb_fine = output_dict.rgb_fine.detach() if 'rgb_fine' in output_dict.keys() else None
+    image = data_dict.image
+    if not _photo_takes_kernel(image, ray_idx, None, (rgb, rgb_fine), None):
+        return mse_on_rays_torch(data_dict, output_dict)
+    image = _rendered_images(image.reshape(len(data_dict.idx), 3, -1), output_dict.idx_img_rendered)
+    nbr = len(output_dict.idx_img_rendered)
+    _, _, _, mse, mse_fine = ops.PhotoReguLoss.apply(image, None, ray_idx, rgb.reshape(nbr, -1, 3), rgb_fine.reshape(nbr, -1, 3) if rgb_fine is not None
+                                                     else None, None, None, None, None, "mse", ops.PHOTO_HUBER_DELTA, 0, 0.001)
+    return mse, (mse_fine if rgb_fine is not None else None)
+
+
+_original_photo = []             # the class's own compute_loss, saved by install_photometric: the distortion hand-over calls it
+
+
+def compute_loss(self, opt, data_dict, output_dict, iteration, mode=None, plot=False, **kwargs):
+    """The method of BasePhotoandReguLoss (base_losses.py:243-323) under its own signature and return convention: reads
+    self.opt.start_iter.photometric, huber_loss_for_photometric and depth_regu_patch_size, opt.loss_weight.fg_mask / depth_patch and
+    opt.nerf.rand_rays.  A config with opt.loss_weight.distortion set goes to the original method, untouched: the distortion loss
+    needs gradients to per-sample weights that the call does not give."""
+    from .edict import EasyDict as edict
+    if opt.loss_weight.distortion is not None:
+        if not _original_photo or _original_photo[-1] is None:
+            raise RuntimeError("sparf_amd.losses.compute_loss: loss_weight.distortion is set and there is no original method to hand it to "
+                               "(install_photometric() saves it)")
+        return _original_photo[-1](self, opt, data_dict, output_dict, iteration, mode=mode, plot=plot, **kwargs)
+    loss_dict = edict(render=torch.tensor(0., requires_grad=True).to(self.device))
+    if iteration < self.opt.start_iter.photometric:
+        return loss_dict, {}, {}
+    batch_size = len(data_dict.idx)
+    assert len(output_dict.idx_img_rendered) == batch_size
+    with_mask, with_patch = opt.loss_weight.fg_mask is not None, opt.loss_weight.depth_patch is not None
+    has = lambda key: output_dict[key] if key in output_dict.keys() else None
+    sampled = (hasattr(opt, 'nerf') and opt.nerf.rand_rays) and mode in ["train", "test-optim"]
+    shape = lambda t, c: t.reshape(batch_size, -1, c) if t is not None else None
+    terms, _ = photo_and_regu_loss(data_dict.image.reshape(batch_size, 3, -1), output_dict.ray_idx if sampled else None,
+                                   shape(output_dict.rgb, 3), shape(has('rgb_fine'), 3),
+                                   fg_mask=data_dict.fg_mask if with_mask else None, opacity=shape(output_dict.opacity, 1) if with_mask else None,
+                                   opacity_fine=shape(has('opacity_fine'), 1) if with_mask else None,
+                                   depth=shape(output_dict['depth'], 1) if with_patch else None,
+                                   depth_fine=shape(has('depth_fine'), 1) if with_patch else None,
+                                   huber=bool(self.opt.huber_loss_for_photometric),
+                                   patch_size=self.opt.depth_regu_patch_size if with_patch else None)
+    loss_dict.update(terms)
+    return loss_dict, {}, {}
+
+
+_patched_photo = []
+
+
+def install_photometric(base_losses_module, trainer_module=None):
+    """Opt-in, and independent of install() and install_depth_consistency(): put compute_loss above on
+    `base_losses_module.BasePhotoandReguLoss` and, with `trainer_module` (a module that imported the name, as nerf_trainer does), mse_on_rays
+    under its `compute_mse_on_rays`, until `uninstall_photometric()`.  Nothing in this package calls it."""
+    if _patched_photo:
+        raise RuntimeError("sparf_amd.losses.install_photometric: already installed; call uninstall_photometric() first")
+    cls = base_losses_module.BasePhotoandReguLoss
+    _original_photo.append(getattr(cls, PHOTO_METHOD, None))
+    _patched_photo.append((cls, PHOTO_METHOD, PHOTO_METHOD in vars(cls), vars(cls).get(PHOTO_METHOD)))
+    setattr(cls, PHOTO_METHOD, compute_loss)
+    if trainer_module is not None:
+        _patched_photo.append((trainer_module, MSE_NAME, MSE_NAME in vars(trainer_module), vars(trainer_module).get(MSE_NAME)))
+        setattr(trainer_module, MSE_NAME, mse_on_rays)
+
+
+def uninstall_photometric():
+    while _patched_photo:
+        obj, name, own, old = _patched_photo.pop()
+        if own:
+            setattr(obj, name, old)
+        else:
+            delattr(obj, name)
+    del _original_photo[:]

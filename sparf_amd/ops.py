@@ -967,6 +967,85 @@ class DconsLoss(torch.autograd.Function):
         return d_zp, None, d_depth, None, d_fine, None, None
 
 
+# ---------------------------------------------------------------------------------------------- photometric, mask and depth-patch loss
+PHOTO_KINDS = {"mse": 0, "huber": 1}                        # include/sparf_hip.h
+PHOTO_HUBER_DELTA = 0.5                                     # base_losses.py:156
+PHOTO_MAX_PATCH = 8                                         # csrc/photo.h PHOTO_MAX_PATCH
+
+
+class PhotoReguLoss(torch.autograd.Function):
+    """BasePhotoandReguLoss.compute_loss (base_losses.py:243-323, :180-194) and compute_mse_on_rays (metrics.py:33-75) in one library
+    call: the ground-truth colours and the mask are gathered in the kernel out of image [B,3,H,W] and fg_mask (bool,
+    B H W elements, or None) by ray_idx ([N] shared, [B,N] per image, or None: full images); rgb / rgb_fine [B,N,3], opacity* and depth*
+    [B,N,1] in any shape of as many elements.  kind "mse" | "huber" (delta), patch = P or 0.  The six seeds that needs_input_grad asks
+    for come from the same launch; the backward multiplies each by the upstream scalar of its own loss and makes no call.
+    -> (render, fg_mask, depth_patch, mse, mse_fine) as 0-dim tensors; a term that is off is 0, mse* are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, image, fg_mask, ray_idx, rgb, rgb_fine, opacity, opacity_fine, depth, depth_fine, kind, delta, patch, charbonnier):
+        op = "photometric loss"
+        dev = rgb.device
+        L.require_gpu(dev)
+        if kind not in PHOTO_KINDS:
+            raise ValueError(f"{op}: kind must be one of {sorted(PHOTO_KINDS)}")
+        patch = int(patch or 0)
+        if image.dim() < 3 or image.shape[1] != 3:
+            raise ValueError(f"{op}: image must be [B,3,H,W] or [B,3,H*W]")
+        B = image.shape[0]
+        HW = image[0, 0].numel() if B else 0
+        if rgb.shape[-1] != 3 or (B and rgb.numel() % (3 * B)):
+            raise ValueError(f"{op}: rgb must be [B,N,3] for the {B} images")
+        rows = rgb.numel() // 3
+        N = rows // B if B else 0
+        per_image = 0
+        if ray_idx is not None:
+            if ray_idx.dtype != torch.int64 or tuple(ray_idx.shape) not in ((N,), (B, N)):
+                raise ValueError(f"{op}: ray_idx must be int64 [{N}] or [{B}, {N}], got {ray_idx.dtype} {list(ray_idx.shape)}")
+            per_image = int(ray_idx.dim() == 2)
+            ray_idx = ray_idx.detach().contiguous()
+        elif N != HW:
+            raise ValueError(f"{op}: without ray_idx the render is of full images: {N} rays for {HW} pixels")
+        if fg_mask is not None:
+            if fg_mask.dtype != torch.bool or fg_mask.numel() != B * HW:
+                raise ValueError(f"{op}: fg_mask must be torch.bool with one element per pixel")
+            if opacity is None:
+                raise ValueError(f"{op}: the mask term needs opacity")
+            fg_mask = fg_mask.detach().contiguous()
+        if patch:
+            if not 0 < patch <= PHOTO_MAX_PATCH:
+                raise ValueError(f"{op}: patch size must be 1..{PHOTO_MAX_PATCH}")
+            if depth is None:
+                raise ValueError(f"{op}: the depth-patch term needs depth")
+            if N % (patch * patch):
+                raise ValueError(f"{op}: {N} rays per image are no whole number of {patch}x{patch} patches")
+        tensors = (rgb, rgb_fine, opacity, opacity_fine, depth, depth_fine)
+        names = ("rgb", "rgb_fine", "opacity", "opacity_fine", "depth", "depth_fine")
+        head = [_flat(t, rows * (3 if i < 2 else 1), name, op, "rays") if t is not None else None for i, (t, name) in enumerate(zip(tensors, names))]
+        out = torch.empty(5, device=dev, dtype=torch.float32)
+        seeds = [torch.empty_like(head[i]) if (t is not None and ctx.needs_input_grad[3 + i]) else None for i, t in enumerate(tensors)]
+        lib = L.load()
+        nb = int(lib.sparf_photo_regu_workspace_bytes(rows))
+        ws = torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None
+        p, img = L.ptr, _f32(image)
+        with L.on(dev):
+            L.check(lib.sparf_photo_regu_loss(p(img), p(fg_mask), p(ray_idx), per_image, B, HW, N, *map(p, head), PHOTO_KINDS[kind],
+                                              float(delta), patch, float(charbonnier), p(out), *map(p, seeds), p(ws), L.stream_ptr(dev)),
+                    "sparf_photo_regu_loss")
+        ctx.save_for_backward(*seeds)
+        ctx.shapes = [t.shape if t is not None else None for t in tensors]
+        ctx.set_materialize_grads(False)
+        render, mask, dpatch, mse, mse_fine = out.unbind(0)
+        ctx.mark_non_differentiable(mse, mse_fine)
+        return render, mask, dpatch, mse, mse_fine
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_render, g_mask, g_patch, *_):
+        ups = (g_render, g_render, g_mask, g_mask, g_patch, g_patch)
+        grads = [_seed(s, shape, g) if g is not None else None for s, shape, g in zip(ctx.saved_tensors, ctx.shapes, ups)]
+        return (None, None, None, *grads, None, None, None, None)
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
 class Composite(torch.autograd.Function):
     """NeRF.composite (frequency_nerf.py:283-343) on caller-built per-sample values (C ABI 6 sparf_composite_forward / _backward):
