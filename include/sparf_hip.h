@@ -326,6 +326,42 @@ int sparf_photo_regu_loss(const float* image, const unsigned char* fg_mask /*NUL
                           float* d_opacity_fine /*NULL ok*/, float* d_depth /*NULL ok*/, float* d_depth_fine /*NULL ok*/,
                           void* workspace /*NULL ok*/, void* stream);
 
+/* ---- correspondence sampler -------------------------------------------------
+ * The torch series of a correspondence iteration between "pair chosen" and its two renders
+ * (source/training/core/base_corres_loss.py:260-269, :323-328, :365-369 and
+ * source/training/core/corres_loss.py:139-155) as two calls.  Integer and copy work: every result
+ * equals the reference's bit for bit.  No atomic, no host synchronisation: `count` is device memory.
+ * sparf_match_compact replaces the centre mask of :260-269, mask.sum() of :365 / :369 and the row
+ *   order of the five boolean selections of corres_loss.py:139-144: pixel p = y W + x of mask[H][W]
+ *   (bytes, torch.bool storage, any alignment) is kept if mask[p] != 0 and y0 <= y < y1 and
+ *   x0 <= x < x1 -- the half-open window of mask_center[H//2-dH : H//2+dH-1, W//2-dW : W//2+dW-1],
+ *   which may be empty; 0, H, 0, W is no window.  index[H W] (int32) receives the flat indices of
+ *   the kept pixels in ascending (row-major) order, the order tensor[mask] produces; count[1] their
+ *   number; perc[1] (NULL ok) (float)count / (float)(H W + 1e-6), the perc_valid_corr_mask of :369.
+ * sparf_match_gather replaces grid[mask], grid_flat[mask], corres[mask], rounded_flat[mask],
+ *   conf[mask] (corres_loss.py:139-144), their five gathers by the permutation (:148-155) and the
+ *   rounding of base_corres_loss.py:326-328, for k rows: with p = index[sel ? sel[j] : j],
+ *   pixels_self[j] = ((float)(p % W), (float)(p / W));  ray_self[j] = p;
+ *   pixels_other[j] = (corres[p], corres[corres_channel_stride + p]) -- the map is read in place,
+ *   channel-first, as corres_maps[i] is stored;  ray_other[j] = (int64)rint(cy) W + (int64)rint(cx)
+ *   of those two values (round half to even, torch.round);  conf_out[j] = conf[p].
+ *   sel (int64, what torch.randperm gives; NULL: the first k entries) holds positions in
+ *   [0, count); one outside is the caller's error and is clamped against the device count, and an
+ *   index entry against H W, so that the launch stays inside the allocations.  No address depends
+ *   on a value read from corres: a non-finite correspondence gives a meaningless ray_other, as in
+ *   the reference, never a fault.  k == 0 launches nothing and looks at no pointer.
+ * workspace: sparf_match_workspace_bytes(H W) bytes (0 up to 4096 pixels: one workgroup, one
+ *   launch; above, a count per chunk of 4096 pixels and two launches; NULL = the one-workgroup path
+ *   at any size).  H W == 0 launches nothing and writes count = 0, perc = 0.
+ * Each returns 1 before any HIP call for a negative size, H W or k above 2^30, a negative channel
+ * stride, or a missing required pointer. */
+int64_t sparf_match_workspace_bytes(int64_t n);
+int sparf_match_compact(const unsigned char* mask, int H, int W, int y0, int y1, int x0, int x1, int32_t* index, int32_t* count,
+                        float* perc /*NULL ok*/, void* workspace /*NULL ok*/, void* stream);
+int sparf_match_gather(const int32_t* index, const int32_t* count, const int64_t* sel /*NULL ok*/, int k, int H, int W,
+                       const float* corres, int64_t corres_channel_stride, const float* conf, float* pixels_self, int64_t* ray_self,
+                       float* pixels_other, int64_t* ray_other, float* conf_out, void* stream);
+
 /* ---- optimiser step ----------------------------------------------------
  * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) (source/training/base.py:96-97,
  * engine after_backward; skipped when max_norm <= 0) followed by torch.optim.Adam.step()

@@ -114,6 +114,9 @@ EXPORTS = {
     "sparf_dcons_loss": (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 6),
     "sparf_photo_regu_workspace_bytes": (c_int64, [c_int64]),
     "sparf_photo_regu_loss": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 6 + [c_int, c_float, c_int, c_float] + [c_void_p] * 9),
+    "sparf_match_workspace_bytes": (c_int64, [c_int64]),
+    "sparf_match_compact": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 5),
+    "sparf_match_gather": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_int64] + [c_void_p] * 7),
     "sparf_adam_workspace_floats": (c_int64, []),
     "sparf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p]),

@@ -1,10 +1,10 @@
-"""The correspondence loss and, below it, the depth-consistency loss and the photometric, mask and
-depth-patch loss.
+"""The correspondence loss and, below it, the depth-consistency loss, the photometric, mask and
+depth-patch loss and the correspondence sampler.
 
 The correspondence loss: SPARF's re-projection of rendered depth at matched pixels through the current relative
 pose (corres_loss.py:50-95, :183-219; batched_geometry_utils.py:199-228; base_losses.py:197-224).
 
-The sampler, the renders and the autograd graph stay PyTorch's.  The BODY -- four re-projection terms and the two compositions of the
+The renders and the autograd graph stay PyTorch's (the sampler: the last section).  The BODY -- four re-projection terms and the two compositions of the
 relative pose -- is one library call behind ops.ReprojLoss / ops.ReprojPairLoss for dense-able float32 tensors on the GPU, and a plain
 torch restatement of the same formulas, in this file, for everything else: CPU, float64, intrinsics / pixels / weights that require a
 gradient (the kernels give none to them), and `unfused()`.  `install()` puts the method under a trainer's own name.  Nothing in this
@@ -19,6 +19,11 @@ device; what is read back is the two ray counts the following renders need on th
 The photometric, mask and depth-patch loss (base_losses.py:243-323, :180-194; metrics.py:33-75) is ONE call, `photo_and_regu_loss`
 (ops.PhotoReguLoss), that gathers the ground-truth pixels in the kernel; `mse_on_rays` is the same call without seeds, and
 `install_photometric()` puts the method and, if asked, the metric under the reference's names.  It reads nothing back.
+
+The correspondence sampler (base_corres_loss.py:260-269, :323-328, :365-369; corres_loss.py:139-155) is `select_matches`:
+an ordered compaction of the valid-correspondence mask (ops.match_compact), one readback of the count, torch.randperm as the reference
+calls it, and one gather of the selected rows (ops.match_gather); `install_sampler()` puts the three methods that hold those lines under
+the reference's names.
 """
 import contextlib
 
@@ -581,3 +586,250 @@ def uninstall_photometric():
         else:
             delattr(obj, name)
     del _original_photo[:]
+
+
+# ================================================================================================ the correspondence sampler
+# what CorrespondenceBasedLoss runs between "pair chosen" and the two renders of compute_loss_on_image_pair
+# (base_corres_loss.py:260-269, :323-328, :365-369; corres_loss.py:139-155) -- the centre mask, the rounded index map of the whole image,
+# mask.sum(), five boolean selections, randperm and five gathers -- as `select_matches`: one ordered compaction (ops.match_compact), ONE
+# readback of the count (the renders need it on the host), torch.randperm as the reference calls it, and one gather (ops.match_gather)
+# that rounds the selected rows only.  Nothing here carries a gradient.  `install_sampler()` puts the three methods that hold those lines
+# under the reference's names.
+SAMPLER_METHODS = ("compute_loss_pairwise", "compute_loss_at_given_img_indexes", "compute_loss_on_image_pair")
+_unfused_sampler = 0
+
+
+@contextlib.contextmanager
+def unfused_sampler():
+    """Inside the block select_matches alone takes its torch restatement; every other function above keeps its route (for comparing the
+    two samplers under the same renders and the same loss kernel)."""
+    global _unfused_sampler
+    _unfused_sampler += 1
+    try:
+        yield
+    finally:
+        _unfused_sampler -= 1
+
+
+def _map_forms(mask, corres_map, conf_map):
+    """-> (mask [H,W], correspondences [H,W,2], confidences [H,W,1]) as the reference indexes them, from any accepted form"""
+    m = mask.detach()
+    m = m.squeeze(-1) if m.dim() == 3 else m
+    H, W = m.shape
+    c = corres_map.detach()
+    c = c if tuple(c.shape) == (H, W, 2) else c.permute(1, 2, 0)
+    f = conf_map.detach()
+    f = f if tuple(f.shape) == (H, W, 1) else f.reshape(H, W, 1)
+    return m, c, f
+
+
+def _empty_matches(device):
+    e = lambda *shape, dtype: torch.empty(*shape, device=device, dtype=dtype)
+    return (e(0, 2, dtype=torch.float32), e(0, dtype=torch.int64), e(0, 2, dtype=torch.float32), e(0, dtype=torch.int64),
+            e(0, 1, dtype=torch.float32))
+
+
+_grids = {}
+
+
+def _pixel_grid(H, W, device):
+    """base_corres_loss.py:45-50 self.grid [H,W,2] and self.grid_flat [H,W]: built once per image size and device, as the reference's
+    constructor does"""
+    key = (H, W, str(device))
+    if key not in _grids:
+        xx = torch.arange(0, W).view(1, -1).repeat(H, 1)
+        yy = torch.arange(0, H).view(-1, 1).repeat(1, W)
+        grid = torch.stack((xx, yy), dim=-1).to(device).float()
+        _grids[key] = (grid, (grid[:, :, 1] * W + grid[:, :, 0]).to(device).long())
+    return _grids[key]
+
+
+def select_matches_torch(mask, corres_map, conf_map, max_matches, *, window=None, perm=None, min_matches=0):
+    """base_corres_loss.py:267-269, :323-328, :365-369 and corres_loss.py:139-155 in the reference's operation order; arguments and
+    results as select_matches"""
+    m, corres, conf = _map_forms(mask, corres_map, conf_map)
+    m = m if m.dtype == torch.bool else m.bool()
+    H, W = m.shape
+    dev = m.device
+    if window is not None:
+        mask_center = torch.zeros_like(m)
+        mask_center[window[0]:window[1], window[2]:window[3]] = 1
+        m = m & mask_center
+    grid, grid_flat = _pixel_grid(H, W, dev)
+    rounded = torch.round(corres).long()
+    rounded_flat = rounded[:, :, 1] * W + rounded[:, :, 0]
+    total = m.sum()
+    # (the reference divides by the Python float; on the device torch then multiplies by the rounded reciprocal, which can differ in the
+    # last bit from the division the CPU does: dividing by a float32 tensor is the CPU's value on either device)
+    perc = total.to(torch.float32) / torch.full((), m.nelement() + 1e-6, dtype=torch.float32, device=dev)
+    count = int(total)
+    if count == 0 or count < min_matches:
+        return (*_empty_matches(dev), count, perc)
+    pixels_self, ray_self = grid[m], grid_flat[m]
+    pixels_other, ray_other, conf_values = corres[m], rounded_flat[m], conf[m]
+    if count > max_matches:
+        random_values = (torch.randperm(count, device=dev) if perm is None else perm)[:max_matches]
+        ray_self, pixels_self = ray_self[random_values], pixels_self[random_values]
+        pixels_other, ray_other, conf_values = pixels_other[random_values], ray_other[random_values], conf_values[random_values]
+    return pixels_self, ray_self, pixels_other, ray_other, conf_values, count, perc
+
+
+def select_matches(mask, corres_map, conf_map, max_matches, *, window=None, perm=None, min_matches=0):
+    """The matches of one view pair that a correspondence iteration renders: the pixels of mask ([H,W] or [H,W,1]) inside window -- (y0,
+    y1, x0, x1) as the slices mask[y0:y1, x0:x1] of base_corres_loss.py:268 read them, None for the whole image -- in row-major order;
+    if there are more than max_matches, the rows perm[:max_matches] of them, with perm = torch.randperm(count, device=mask.device) when
+    none is given (the reference's own call: the same seed draws the same matches and leaves the generator in the same state).
+    corres_map [H,W,2] (the reference's permuted view; read in place) or channel-first [2,H,W]; conf_map [H,W,1], [1,H,W] or [H,W].
+    -> (pixels_self [k,2] float32, ray_self [k] int64, pixels_other [k,2] float32, ray_other [k] int64: the flat index of the rounded
+    correspondence, conf [k,1] float32, count: a Python int, the ONE readback, perc_valid = count / (H W + 1e-6) as a 0-dim tensor).
+    With count == 0 or count < min_matches the five tensors are empty and nothing is drawn or gathered."""
+    if (_unfused_sampler or mask.dtype != torch.bool or corres_map.dtype != torch.float32 or conf_map.dtype != torch.float32 or
+            not _takes_kernel((corres_map, conf_map), (mask,))):
+        return select_matches_torch(mask, corres_map, conf_map, max_matches, window=window, perm=perm, min_matches=min_matches)
+    H, W = mask.shape[:2]
+    index, count_dev, perc = ops.match_compact(mask, window)
+    count = int(count_dev.item()) if H * W else 0         # the one readback
+    perc = perc[0]
+    if count == 0 or count < min_matches:
+        return (*_empty_matches(mask.device), count, perc)
+    sel = None
+    if count > max_matches:
+        sel = (torch.randperm(count, device=mask.device) if perm is None else perm)[:max_matches]
+    rows = ops.match_gather(index, count_dev, sel, min(count, max_matches), H, W, corres_map, conf_map)
+    return (*rows, count, perc)
+
+
+_original_sampler = {}           # the classes' own methods, saved by install_sampler: the debug configurations are handed to them
+
+
+def _opt(opt, key, default=None):
+    return getattr(opt, key, default) if not isinstance(opt, dict) else opt.get(key, default)
+
+
+def _handed_over(self, name):
+    if _original_sampler.get(name) is None:
+        raise RuntimeError(f"sparf_amd.losses.{name}: a debug configuration (use_gt_correspondences / skip_verif=False) and there is no "
+                           "original method to hand it to (install_sampler() saves it)")
+    return _original_sampler[name]
+
+
+def _window_mask_torch(mask, window):
+    if window is None:
+        return mask
+    mask_center = torch.zeros_like(mask)
+    mask_center[window[0]:window[1], window[2]:window[3]] = 1
+    return mask & mask_center
+
+
+def compute_loss_pairwise(self, opt, data_dict, output_dict, iteration, mode=None, plot=False):
+    """The method of CorrespondenceBasedLoss (base_corres_loss.py:217-273) under its own signature and return convention: the pre-crop
+    phase hands the window of :268 on instead of building mask_center."""
+    if _opt(self.opt, 'use_gt_correspondences', False):
+        return _handed_over(self, SAMPLER_METHODS[0])(self, opt, data_dict, output_dict, iteration, mode, plot)
+    zero = lambda: torch.tensor(0., requires_grad=True).to(self.device)
+    stats_dict, plotting_dict, loss_dict = {}, {}, {'corres': zero(), 'render_matches': zero()}
+    if mode != 'train' or iteration < self.opt.start_iter.corres or len(self.filtered_flow_pairs) == 0:
+        return loss_dict, stats_dict, plotting_dict
+    id_self, id_matching_view, corres_map, conf_map, variance, mask = self.sample_valid_image_pair()
+    window = None
+    if iteration < self.opt.precrop_iters:
+        H, W = data_dict.image.shape[-2:]
+        dH, dW = int(H // 2 * self.opt.precrop_frac), int(W // 2 * self.opt.precrop_frac)
+        window = (H // 2 - dH, H // 2 + dH - 1, W // 2 - dW, W // 2 + dW - 1)
+    return self.compute_loss_at_given_img_indexes(opt, data_dict, id_self, id_matching_view, corres_map, conf_map, variance, mask, loss_dict,
+                                                  stats_dict, plotting_dict, plot, **({} if window is None else dict(window=window)))
+
+
+def compute_loss_at_given_img_indexes(self, opt, data_dict, id_self, id_matching_view, corres_map_self_to_other_, conf_map_self_to_other_,
+                                      variance_self_to_other_, mask_correct_corr, loss_dict, stats_dict, plotting_dict, plot=False,
+                                      skip_verif=True, window=None):
+    """The method of CorrespondenceBasedLoss (base_corres_loss.py:275-374) under its own signature and return convention, with `window`
+    (see select_matches) in addition.  The rounded index map of the whole image and the mask.sum() readback are gone: the
+    min_nbr_matches test and the perc_valid_corr_mask stat sit behind the one readback of compute_loss_on_image_pair."""
+    if not skip_verif or _opt(self.opt, 'use_gt_correspondences', False):
+        return _handed_over(self, SAMPLER_METHODS[1])(self, opt, data_dict, id_self, id_matching_view, corres_map_self_to_other_,
+                                                      conf_map_self_to_other_, variance_self_to_other_,
+                                                      _window_mask_torch(mask_correct_corr, window), loss_dict, stats_dict, plotting_dict, plot,
+                                                      skip_verif)
+    images = data_dict.image.permute(0, 2, 3, 1)
+    poses_w2c, intrs = data_dict.poses_w2c, data_dict.intr
+    pose_w2c_self, pose_w2c_other = _to_4x4(poses_w2c[id_self]), _to_4x4(poses_w2c[id_matching_view])
+    return self.compute_loss_on_image_pair(data_dict, images, poses_w2c, intrs, id_self, id_matching_view, corres_map_self_to_other_.detach(), None,
+                                           conf_map_self_to_other_.detach(), mask_correct_corr.detach().squeeze(-1), pose_w2c_self,
+                                           pose_w2c_other, intrs[id_self], intrs[id_matching_view], loss_dict, stats_dict, plotting_dict,
+                                           **({} if window is None else dict(window=window)))
+
+
+def compute_loss_on_image_pair(self, data_dict, images, poses_w2c, intrs, id_self, id_matching_view, corres_map_self_to_other,
+                               corres_map_self_to_other_rounded_flat, conf_map_self_to_other, mask_correct_corr, pose_w2c_self, pose_w2c_other,
+                               intr_self, intr_other, loss_dict, stats_dict, plotting_dict, window=None):
+    """The method of CorrespondencesPairRenderDepthAndGet3DPtsAndReproject (corres_loss.py:97-220) under its own signature and return
+    convention, with `window` in addition: select_matches, the two renders, correspondence_pair_loss.  The rounded index map it is
+    handed is ignored (None is fine) and recomputed for the selected rows; the min_nbr_matches test of base_corres_loss.py:365-369 is
+    made here, on the count that is read back anyway, and below it the dictionaries come back untouched."""
+    if _opt(self.opt, 'use_gt_correspondences', False):
+        return _handed_over(self, SAMPLER_METHODS[2])(self, data_dict, images, poses_w2c, intrs, id_self, id_matching_view, corres_map_self_to_other,
+                                                      corres_map_self_to_other_rounded_flat, conf_map_self_to_other,
+                                                      _window_mask_torch(mask_correct_corr, window), pose_w2c_self, pose_w2c_other, intr_self,
+                                                      intr_other, loss_dict, stats_dict, plotting_dict)
+    iteration = data_dict['iter']
+    B, H, W = images.shape[:3]
+    min_matches = _opt(self.opt, 'min_nbr_matches', 0)
+    pixels_self, ray_self, pixels_other, ray_other, conf_values, count, perc = select_matches(
+        mask_correct_corr, corres_map_self_to_other, conf_map_self_to_other, self.opt.nerf.rand_rays // 2, window=window, min_matches=min_matches)
+    if count < min_matches:
+        return loss_dict, stats_dict, plotting_dict
+    stats_dict['perc_valid_corr_mask'] = perc
+    render = lambda pose, intr, pixels: self.net.render_image_at_specific_pose_and_rays(self.opt, data_dict, pose[:3], intr, H, W, pixels=pixels,
+                                                                                       mode='train', iter=iteration)
+    ret_self = render(pose_w2c_self, intr_self, pixels_self)
+    ret_other = render(pose_w2c_other, intr_other, pixels_other)
+    if _opt(self.opt, 'compute_photo_on_matches', False):
+        image_self = images[id_self].view(-1, 3)[ray_self]
+        image_other = images[id_matching_view].view(-1, 3)[ray_other]
+        loss_photo_self = self.MSE_loss(ret_self.rgb.view(-1, 3), image_self)
+        loss_photo_other = self.MSE_loss(ret_other.rgb.view(-1, 3), image_other)
+        if 'rgb_fine' in ret_self.keys():
+            loss_photo_self += self.MSE_loss(ret_self.rgb_fine.view(-1, 3), image_self)
+            loss_photo_other += self.MSE_loss(ret_other.rgb_fine.view(-1, 3), image_other)
+        loss_dict['render_matches'] += (loss_photo_other + loss_photo_self) / 2.
+    fine = 'depth_fine' in ret_other.keys()
+    flat = lambda d: d.squeeze(0).squeeze(-1)
+    pixel_thresh = self.opt.renderrepro_pixel_reprojection_thresh if self.opt.renderrepro_do_pixel_reprojection_check else None
+    depth_thresh = self.opt.renderrepro_depth_reprojection_thresh if self.opt.renderrepro_do_depth_reprojection_check else None
+    loss, stats = correspondence_pair_loss(pixels_self, pixels_other, flat(ret_self.depth), flat(ret_other.depth), intr_self, intr_other,
+                                           pose_w2c_self, pose_w2c_other, conf_values, flat(ret_self.depth_fine) if fine else None,
+                                           flat(ret_other.depth_fine) if fine else None, loss_type=self.opt.diff_loss_type,
+                                           pixel_thresh=pixel_thresh, depth_thresh=depth_thresh)
+    stats_dict.update(stats)
+    loss_dict['corres'] = loss
+    return loss_dict, stats_dict, plotting_dict
+
+
+_patched_sampler = []
+
+
+def install_sampler(corres_loss_module, base_corres_loss_module):
+    """Opt-in, and independent of install(), install_depth_consistency() and install_photometric(): put compute_loss_pairwise and
+    compute_loss_at_given_img_indexes above on `base_corres_loss_module.CorrespondenceBasedLoss` and compute_loss_on_image_pair on
+    `corres_loss_module.CorrespondencesPairRenderDepthAndGet3DPtsAndReproject`, until `uninstall_sampler()`.  A module configured with
+    use_gt_correspondences, or a call with skip_verif=False, goes to the original methods.  Nothing in this package calls it."""
+    if _patched_sampler:
+        raise RuntimeError("sparf_amd.losses.install_sampler: already installed; call uninstall_sampler() first")
+    base = base_corres_loss_module.CorrespondenceBasedLoss
+    pair = corres_loss_module.CorrespondencesPairRenderDepthAndGet3DPtsAndReproject
+    new = dict(zip(SAMPLER_METHODS, (compute_loss_pairwise, compute_loss_at_given_img_indexes, compute_loss_on_image_pair)))
+    for cls, name in ((base, SAMPLER_METHODS[0]), (base, SAMPLER_METHODS[1]), (pair, SAMPLER_METHODS[2])):
+        _original_sampler[name] = getattr(cls, name, None)
+        _patched_sampler.append((cls, name, name in vars(cls), vars(cls).get(name)))
+        setattr(cls, name, new[name])
+
+
+def uninstall_sampler():
+    while _patched_sampler:
+        obj, name, own, old = _patched_sampler.pop()
+        if own:
+            setattr(obj, name, old)
+        else:
+            delattr(obj, name)
+    _original_sampler.clear()

@@ -1046,6 +1046,100 @@ class PhotoReguLoss(torch.autograd.Function):
         return (None, None, None, *grads, None, None, None, None)
 
 
+# ---------------------------------------------------------------------------------------------- correspondence sampler
+# SURVEY 8f next-9.  Plain functions: nothing here carries a gradient (every input is detached in the reference).
+def match_window(window, H, W):
+    """(y0, y1, x0, x1) as the Python slices mask[y0:y1, x0:x1] read them -> the same half-open window with 0 <= y0, y1 <= H, 0 <= x0,
+    x1 <= W (an empty one stays empty); None -> the whole image"""
+    if window is None:
+        return 0, H, 0, W
+    y0, y1, _ = slice(int(window[0]), int(window[1])).indices(H)
+    x0, x1, _ = slice(int(window[2]), int(window[3])).indices(W)
+    return y0, y1, x0, x1
+
+
+def _match_mask(mask):
+    """the mask [H,W] or [H,W,1] (torch.bool) as H W bytes in row-major order -> (tensor, H, W); dense already in every form the
+    reference hands over (a slice of [M,1,H,W], permuted), made dense once otherwise"""
+    if mask.dtype != torch.bool or mask.dim() not in (2, 3) or (mask.dim() == 3 and mask.shape[-1] != 1):
+        raise ValueError(f"correspondence sampler: the mask must be torch.bool [H,W] or [H,W,1], got {mask.dtype} {list(mask.shape)}")
+    m = mask.detach()
+    m = m[..., 0] if m.dim() == 3 else m
+    return (m if m.is_contiguous() else m.contiguous()), m.shape[0], m.shape[1]
+
+
+def _match_corres(corres, H, W):
+    """the correspondence map as [H,W,2] (the reference's permuted view of a channel-first map, read in place) or channel-first
+    [2,H,W] -> (tensor whose data_ptr is x of pixel 0, channel stride in elements); any other float32 layout is made dense once"""
+    c = corres.detach()
+    if tuple(c.shape) == (H, W, 2):
+        c = c.permute(2, 0, 1)
+    elif tuple(c.shape) != (2, H, W):
+        raise ValueError(f"correspondence sampler: the correspondence map must be [{H},{W},2] or [2,{H},{W}], got {list(corres.shape)}")
+    if c.dtype != torch.float32:
+        raise ValueError("correspondence sampler: the correspondence map must be float32")
+    planar = H * W <= 1 or (c[0].is_contiguous() and c.stride(0) >= 0)
+    if not planar:
+        c = c.contiguous()
+    return c, int(c.stride(0)) if H * W else 0
+
+
+def _match_conf(conf, H, W):
+    """the confidence map [H,W,1], [1,H,W] or [H,W] as H W floats in row-major order"""
+    c = conf.detach()
+    if c.dtype != torch.float32 or c.numel() != H * W or tuple(c.shape) not in ((H, W, 1), (1, H, W), (H, W)):
+        raise ValueError(f"correspondence sampler: the confidence map must be float32 [{H},{W},1], [1,{H},{W}] or [{H},{W}], got "
+                         f"{c.dtype} {list(conf.shape)}")
+    c = c.reshape(H, W)                                  # (dropping a dimension of one element is a view)
+    return c if c.is_contiguous() else c.contiguous()
+
+
+def match_compact(mask, window=None, want_perc=True):
+    """sparf_match_compact: the pixels of mask (torch.bool [H,W] or [H,W,1]) inside window -> (index [H W] int32 whose first count
+    entries are their flat indices in row-major order, count [1] int32, perc [1] float32 or None), all on the device: no readback"""
+    m, H, W = _match_mask(mask)
+    dev = m.device
+    L.require_gpu(dev)
+    y0, y1, x0, x1 = match_window(window, H, W)
+    n = H * W
+    index = torch.empty(n, device=dev, dtype=torch.int32)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    perc = torch.empty(1, device=dev, dtype=torch.float32) if want_perc else None
+    lib = L.load()
+    nb = int(lib.sparf_match_workspace_bytes(n))
+    ws = torch.empty(nb // 4, device=dev, dtype=torch.int32) if nb else None
+    p = L.ptr
+    with L.on(dev):
+        L.check(lib.sparf_match_compact(p(m), H, W, y0, y1, x0, x1, p(index), p(count), p(perc), p(ws), L.stream_ptr(dev)), "sparf_match_compact")
+    return index, count, perc
+
+
+def match_gather(index, count, sel, k, H, W, corres, conf):
+    """sparf_match_gather for k rows: index / count as match_compact left them, sel int64 [k] positions in index or None (the first k),
+    the maps in the forms of _match_corres / _match_conf.  -> (pixels_self [k,2] float32, ray_self [k] int64, pixels_other [k,2]
+    float32, ray_other [k] int64, conf [k,1] float32).  k == 0: empty tensors, no call."""
+    dev = index.device
+    k = int(k)
+    f32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+    i64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int64)
+    outs = (f32(k, 2), i64(k), f32(k, 2), i64(k), f32(k, 1))
+    if k == 0:
+        return outs
+    L.require_gpu(dev)
+    if sel is not None:
+        if sel.dtype != torch.int64 or sel.numel() != k:
+            raise ValueError(f"correspondence sampler: the selection must be int64 [{k}], got {sel.dtype} {list(sel.shape)}")
+        sel = sel.detach().reshape(-1).contiguous()
+    c, stride = _match_corres(corres, H, W)
+    cf = _match_conf(conf, H, W)
+    lib = L.load()
+    p = L.ptr
+    with L.on(dev):
+        L.check(lib.sparf_match_gather(p(index), p(count), p(sel), k, H, W, ctypes.c_void_p(c.data_ptr()), stride, p(cf), *map(p, outs),
+                                       L.stream_ptr(dev)), "sparf_match_gather")
+    return outs
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
 class Composite(torch.autograd.Function):
     """NeRF.composite (frequency_nerf.py:283-343) on caller-built per-sample values (C ABI 6 sparf_composite_forward / _backward):
