@@ -362,6 +362,54 @@ int sparf_match_gather(const int32_t* index, const int32_t* count, const int64_t
                        const float* corres, int64_t corres_channel_stride, const float* conf, float* pixels_self, int64_t* ray_self,
                        float* pixels_other, int64_t* ray_other, float* conf_out, void* stream);
 
+/* ---- evaluation metrics ----------------------------------------------------
+ * compute_metrics / compute_metrics_masked / compute_depth_error (source/training/core/metrics.py:
+ * 136-268, called per head by source/training/base.py:475-499 and nerf_trainer.py:387-405) with the
+ * SSIM of third_party/pytorch_ssim/ssim.py:8-50 (window 11, sigma 1.5, padding 5, size_average) as
+ * ONE call on B images of H x W, three channels: one or two predictions against one ground truth.
+ * LPIPS is not part of it.  Arithmetic as above: double on the fp32 operands, sums in double in a
+ * fixed order (thread, wave butterfly, waves, tiles in tile order), one rounding per stored value,
+ * no atomic, no host synchronisation: the same bits from call to call.
+ * Operands are read in place by ELEMENT strides, none negative: the images by (batch, channel, row,
+ *   column) -- a channel-last render under a permuted [B,3,H,W] view and a channel-first ground
+ *   truth alike --, fg_mask [B][H][W] (bytes 0 / 1) by (batch, row, column), the depth rows
+ *   [B][H W] by (batch, pixel).  pred_fine NULL: one head.
+ * SSIM: the 11 x 11 window runs separably (rows, then columns) over the five moment maps, zero
+ *   outside the image.  With fg_mask both images are composited first, x m + (1 - m), and padded
+ *   with zero after that (metrics.py:208-212).
+ * Depth (metrics.py:158-184): over the pixels with valid_depth_gt != 0 (NULL: every pixel),
+ *   e = depth_gt - s depth at s = 1 and at s = depth_scale.
+ * out[2][10], one row per head: mse, psnr = -10 log10 mse, ssim -- means over all 3 B H W
+ *   elements --; mse_masked (over the foreground elements), psnr_masked, ssim_masked (the mean of
+ *   the composites' SSIM map); abs_e = sum |e| / (n + 1e-6), rmse = sqrt(sum e^2 / n) at s = 1;
+ *   abs_e_scaled, rmse_scaled at depth_scale.  mse == 0 gives psnr +inf; no foreground pixel gives
+ *   mse_masked and psnr_masked NaN; no valid pixel gives abs_e 0 and rmse NaN; what was not asked
+ *   for (no second head, no mask, no depth of that head) is NaN.
+ * counts[2]: foreground pixels, valid depth pixels (0 without fg_mask / depth_gt).
+ * workspace: sparf_image_metrics_workspace_bytes(B, H, W) bytes -- the partial totals of every
+ *   16 x 32 tile --, 0 for sizes the call refuses.  Two launches: the tiles, then their sum.
+ * Returns 1 before any HIP call for a NULL argument or required pointer (pred, gt, out, counts,
+ * workspace), B, H or W < 1, B H W above 2^30, a negative stride, depth or depth_fine without
+ * depth_gt, depth_fine without pred_fine, or workspace_bytes below what the size needs. */
+typedef struct {
+    int B, H, W;
+    const float* pred;                      int64_t pred_stride[4];
+    const float* pred_fine; /*NULL ok*/     int64_t pred_fine_stride[4];
+    const float* gt;                        int64_t gt_stride[4];
+    const unsigned char* fg_mask; /*NULL ok*/        int64_t fg_mask_stride[3];
+    const float* depth; /*NULL ok*/         int64_t depth_stride[2];
+    const float* depth_fine; /*NULL ok*/    int64_t depth_fine_stride[2];
+    const float* depth_gt; /*NULL ok*/      int64_t depth_gt_stride[2];
+    const unsigned char* valid_depth_gt; /*NULL ok*/ int64_t valid_depth_gt_stride[2];
+    float depth_scale;
+    float* out;                             /* [2][10] */
+    int32_t* counts;                        /* [2] */
+    void* workspace;
+    int64_t workspace_bytes;
+} sparf_image_metrics_t;
+int64_t sparf_image_metrics_workspace_bytes(int B, int H, int W);
+int sparf_image_metrics(const sparf_image_metrics_t* m, void* stream);
+
 /* ---- optimiser step ----------------------------------------------------
  * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) (source/training/base.py:96-97,
  * engine after_backward; skipped when max_norm <= 0) followed by torch.optim.Adam.step()

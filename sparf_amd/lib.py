@@ -85,6 +85,15 @@ class CompositeBwd(ctypes.Structure):
                 ("d_density", c_void_p), ("d_rgb_samples", c_void_p), ("d_dir", c_void_p), ("d_len_ws", c_void_p)]
 
 
+class ImageMetrics(ctypes.Structure):                   # include/sparf_hip.h sparf_image_metrics_t
+    _fields_ = [("B", c_int), ("H", c_int), ("W", c_int),
+                ("pred", c_void_p), ("pred_stride", c_int64 * 4), ("pred_fine", c_void_p), ("pred_fine_stride", c_int64 * 4),
+                ("gt", c_void_p), ("gt_stride", c_int64 * 4), ("fg_mask", c_void_p), ("fg_mask_stride", c_int64 * 3),
+                ("depth", c_void_p), ("depth_stride", c_int64 * 2), ("depth_fine", c_void_p), ("depth_fine_stride", c_int64 * 2),
+                ("depth_gt", c_void_p), ("depth_gt_stride", c_int64 * 2), ("valid_depth_gt", c_void_p), ("valid_depth_gt_stride", c_int64 * 2),
+                ("depth_scale", c_float), ("out", c_void_p), ("counts", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64)]
+
+
 EXPORTS = {
     "sparf_abi_version": (c_int, []),
     "sparf_table_count": (c_int64, [c_int]),
@@ -117,6 +126,8 @@ EXPORTS = {
     "sparf_match_workspace_bytes": (c_int64, [c_int64]),
     "sparf_match_compact": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 5),
     "sparf_match_gather": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_int64] + [c_void_p] * 7),
+    "sparf_image_metrics_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "sparf_image_metrics": (c_int, [POINTER(ImageMetrics), c_void_p]),
     "sparf_adam_workspace_floats": (c_int64, []),
     "sparf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p]),

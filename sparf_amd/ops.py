@@ -1140,6 +1140,74 @@ def match_gather(index, count, sel, k, H, W, corres, conf):
     return outs
 
 
+# ---------------------------------------------------------------------------------------------- evaluation metrics
+# SURVEY 8f next-10.  A plain function: evaluation carries no gradient.
+METRICS_OUTS = ("mse", "psnr", "ssim", "mse_masked", "psnr_masked", "ssim_masked", "abs_e", "rmse", "abs_e_scaled", "rmse_scaled")     # csrc/metrics.h
+
+
+def _metrics_image(t, B, H, W, name):
+    """an image [B,3,H,W] float32 in whatever strides it comes (a permuted channel-last render, an offset slice): read in place; only
+    a view with a negative stride (none of torch's) would be made dense"""
+    if t.dtype != torch.float32 or tuple(t.shape) != (B, 3, H, W):
+        raise ValueError(f"image metrics: {name} must be float32 [{B},3,{H},{W}], got {t.dtype} {list(t.shape)}")
+    t = t.detach()
+    return t if all(s >= 0 for s in t.stride()) else t.contiguous()
+
+
+def _metrics_rows(t, B, HW, dtypes, name):
+    """depth [B, H W] in any shape of as many elements per image (float32), or a validity mask (bool / uint8) -> [B, HW] view"""
+    if t.dtype not in dtypes or t.shape[0] != B or t.numel() != B * HW:
+        raise ValueError(f"image metrics: {name} must be {dtypes[0]} with {HW} elements for each of the {B} images, got {t.dtype} {list(t.shape)}")
+    return t.detach().reshape(B, HW)
+
+
+def image_metrics(pred, gt, pred_fine=None, fg_mask=None, depth=None, depth_fine=None, depth_gt=None, valid_depth_gt=None, depth_scale=1.0):
+    """sparf_image_metrics: pred / pred_fine / gt float32 [B,3,H,W] in any strides; fg_mask torch.bool or uint8 0/1, B H W elements
+    ([B,H,W] or [B,1,H,W]); depth / depth_fine / depth_gt float32 and valid_depth_gt bool, H W elements per image.
+    -> (out [2,10] float32: a row per head in the order of METRICS_OUTS, NaN for what was not asked for; counts [2] int32: foreground
+    pixels, valid depth pixels), on the device: two launches, no readback"""
+    if gt.dim() != 4 or gt.shape[1] != 3:
+        raise ValueError(f"image metrics: gt must be [B,3,H,W], got {list(gt.shape)}")
+    B, _, H, W = gt.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"image metrics: empty images {list(gt.shape)}")
+    dev = gt.device
+    L.require_gpu(dev)
+    if (depth is not None or depth_fine is not None) and depth_gt is None:
+        raise ValueError("image metrics: a depth needs depth_gt")
+    if depth_fine is not None and pred_fine is None:
+        raise ValueError("image metrics: depth_fine needs pred_fine")
+    a = L.ImageMetrics(B=B, H=H, W=W, depth_scale=float(depth_scale))
+    keep = []
+
+    def put(name, t):
+        keep.append(t)
+        setattr(a, name, t.data_ptr())
+        getattr(a, name + "_stride")[:] = t.stride()
+
+    put("pred", _metrics_image(pred, B, H, W, "pred"))
+    put("gt", _metrics_image(gt, B, H, W, "gt"))
+    if pred_fine is not None:
+        put("pred_fine", _metrics_image(pred_fine, B, H, W, "pred_fine"))
+    if fg_mask is not None:
+        if fg_mask.dtype not in (torch.bool, torch.uint8) or fg_mask.numel() != B * H * W or fg_mask.shape[0] != B:
+            raise ValueError(f"image metrics: fg_mask must be torch.bool (or 0/1 bytes) with one element per pixel, got {fg_mask.dtype} {list(fg_mask.shape)}")
+        put("fg_mask", fg_mask.detach().reshape(B, H, W))
+    for name, t, dtypes in (("depth", depth, (torch.float32,)), ("depth_fine", depth_fine, (torch.float32,)), ("depth_gt", depth_gt, (torch.float32,)),
+                            ("valid_depth_gt", valid_depth_gt if depth_gt is not None else None, (torch.bool, torch.uint8))):
+        if t is not None:
+            put(name, _metrics_rows(t, B, H * W, dtypes, name))
+    out = torch.empty(2, len(METRICS_OUTS), device=dev, dtype=torch.float32)
+    counts = torch.empty(2, device=dev, dtype=torch.int32)
+    lib = L.load()
+    nb = int(lib.sparf_image_metrics_workspace_bytes(B, H, W))
+    ws = torch.empty(max(nb // 8, 1), device=dev, dtype=torch.float64)
+    a.out, a.counts, a.workspace, a.workspace_bytes = out.data_ptr(), counts.data_ptr(), ws.data_ptr(), nb
+    with L.on(dev):
+        L.check(lib.sparf_image_metrics(ctypes.byref(a), L.stream_ptr(dev)), "sparf_image_metrics")
+    return out, counts
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
 class Composite(torch.autograd.Function):
     """NeRF.composite (frequency_nerf.py:283-343) on caller-built per-sample values (C ABI 6 sparf_composite_forward / _backward):

@@ -576,6 +576,24 @@ class Graph(torch.nn.Module):
             out.update(mse_fine=mse[1], psnr_fine=-10 * mse[1].log10())
         return out
 
+    @torch.no_grad()
+    def evaluate_metrics(self, opt, pose, H, W, intr, depth_range, image, iter=None, mode="val", fg_mask=None, depth_gt=None,
+                         valid_depth_gt=None, depth_scale=1.0):
+        """Full-image evaluation with every metric the reference's trainers log for a view (metrics.py:136-268 as
+        nerf_trainer.py:387-405 calls it per head): `render_by_slices`, of which only rgb / depth (and their `_fine`) are kept, then
+        ONE `metrics.image_metrics` call for both heads on the channel-last renders read in place.  `image` [B,3,H,W]; fg_mask (bool,
+        [B,1,H,W]) adds the masked metrics; depth_gt / valid_depth_gt [B,1,H,W] and depth_scale the depth errors.
+        -> the dict of `metrics.image_metrics`: 0-dim device tensors, no readback.  LPIPS is not part of it."""
+        from . import metrics
+        B = len(pose)
+        ret = self.render_by_slices(opt, pose, H, W, intr, depth_range, iter, mode=mode)
+        fine = ret.get("rgb_fine") is not None
+        as_image = lambda rgb: rgb.view(B, H, W, 3).permute(0, 3, 1, 2)
+        with_depth = depth_gt is not None
+        return metrics.image_metrics(as_image(ret.rgb), image.reshape(B, 3, H, W), pred_fine=as_image(ret.rgb_fine) if fine else None, fg_mask=fg_mask,
+                                     depth=ret.depth if with_depth else None, depth_fine=ret.depth_fine if (with_depth and fine) else None,
+                                     depth_gt=depth_gt, valid_depth_gt=valid_depth_gt if with_depth else None, depth_scale=depth_scale)
+
     # ------------------------------------------------------------------ depth sampling
     def sample_depth(self, opt, batch_size, n_samples, H, W, depth_range, num_rays=None, mode=None):
         """Stratified samples along every ray, same range for all rays (renderer.py:383-419).
