@@ -410,6 +410,58 @@ typedef struct {
 int64_t sparf_image_metrics_workspace_bytes(int B, int H, int W);
 int sparf_image_metrics(const sparf_image_metrics_t* m, void* stream);
 
+/* ---- pose evaluation ---------------------------------------------------
+ * CommonPoseEvaluation.evaluate_any_poses (source/training/joint_pose_nerf_trainer.py:290-311)
+ * with prealign_w2c_small_camera_systems (:160-254, its alignment_function :173-213) and
+ * evaluate_camera_alignment (:257-287, rotation_distance of source/utils/camera.py:466-471) as
+ * ONE launch on S sets of B world-to-camera poses; and backtrack_from_aligning_the_trajectory
+ * (source/utils/geometry/align_trajectories.py:94-101) as one more.  Arithmetic as above: double
+ * on the fp32 operands, one rounding per stored value, no atomic, no host synchronisation: the
+ * same bits from call to call.
+ * Candidates: every ordered pair (a, b), a != b, of the first n = min(B, 10) views, a outermost
+ *   (:233-236); candidate p scales the estimated camera centres by |c_gt[a] - c_gt[b]| /
+ *   |c[a] - c[b]|, applies T = GT_c2w[a] o inverse(scaled[a]) to all B poses and scores the
+ *   result by (mean rotation error in degrees, mean centre distance, their product), means in
+ *   index order.  The rotation error clamps at the reference's bound as its fp32 tensor holds
+ *   it, (float)(1 - 1e-7).  The choice is np.argmin on the products (:249): the lowest index
+ *   that is NaN if any is, otherwise the lowest index of the minimum.
+ * flags: SPARF_POSE_EVAL_ALIGN runs the search; without it (n_first_fixed_poses > 1, :219-223, or
+ *   a bare evaluate_camera_alignment) the aligned poses are the inputs, the similarity is the
+ *   identity with s = 1, and best is -1.
+ * pose[S][B][12]; pose_gt[gt_sets][B][12] with gt_sets 1 (shared) or S.
+ * stats[S][4]: error_R_before_align (degrees), error_t_before_align, error_R (degrees), error_t
+ *   (:299-311).  errors[S][2][B][2]: before / after alignment x (rotation error in radians,
+ *   centre distance) of every pose.  aligned[S][B][12]: the chosen candidate's aligned
+ *   world-to-camera poses.  sim3[S][13]: its R (9, rows), t (3) and s, the reference's
+ *   ssim_est_gt_c2w (:210-211).  best[S]: its index.  scores[S][90][3] (NULL ok): the triple of
+ *   every candidate; rows from n (n - 1) on are left untouched.
+ * Returns 0 without a launch for S == 0; 1 before any HIP call for a NULL struct or required
+ * pointer, S or B < 0, B == 0, B > 64 (SPARF_POSE_EVAL_MAX_POSES: the caller takes another path),
+ * gt_sets not 1 or S, an unknown flag, or SPARF_POSE_EVAL_ALIGN with B < 2. */
+#define SPARF_POSE_EVAL_ALIGN 1
+#define SPARF_POSE_EVAL_MAX_POSES 64
+#define SPARF_POSE_EVAL_MAX_PAIRS 90
+typedef struct {
+    const float* pose;
+    const float* pose_gt;
+    int gt_sets;
+    int S, B, flags;
+    float* stats;
+    float* errors;
+    float* aligned;
+    float* sim3;
+    int32_t* best;
+    float* scores; /*NULL ok*/
+} sparf_pose_eval_t;
+int sparf_pose_eval(const sparf_pose_eval_t* e, void* stream);
+/* align_trajectories.py:94-101 on n poses, forward only (the reference runs it under no_grad on
+ * ground-truth poses): out = invert([R^T R_c | (R^T / s) (t_c - t)]), [R_c | t_c] =
+ * invert(pose_gt_w2c).  sim3: 13 floats (R rows, t, s) on the device, every sim3_stride floats
+ * (0: one similarity for all poses).  n == 0 returns 0 without a launch; n < 0, a negative
+ * stride or a missing pointer returns 1. */
+int sparf_pose_backtrack(const float* pose_gt_w2c, int n, const float* sim3, int sim3_stride,
+                         float* out, void* stream);
+
 /* ---- optimiser step ----------------------------------------------------
  * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) (source/training/base.py:96-97,
  * engine after_backward; skipped when max_norm <= 0) followed by torch.optim.Adam.step()

@@ -18,6 +18,10 @@ int launch_pose_compose_fwd(const float* a, const float* b, int n, float* out, h
 int launch_pose_compose_bwd(const float* a, const float* b, int n, const float* d_out, float* d_a, float* d_b, hipStream_t s);
 int launch_pose_d9_fwd(const float* d9, int invert, int n, float* pose_out, hipStream_t s);
 int launch_pose_d9_bwd(const float* d9, int invert, int n, const float* d_pose, float* d_d9, hipStream_t s);
+// pose_eval.hip
+int launch_pose_eval(const float* pose, const float* pose_gt, int gt_sets, int S, int B, int align, float* stats, float* errors, float* aligned,
+                     float* sim3, int* best, float* scores, hipStream_t s);
+int launch_pose_backtrack(const float* pose_gt_w2c, int n, const float* sim3, int sim3_stride, float* out, hipStream_t s);
 // reproj.hip: n > 0
 int64_t reproj_workspace_bytes(int n);
 int launch_reproj(const ReprojArgs& a, hipStream_t s);
@@ -170,6 +174,25 @@ int sparf_pose_d9_backward(const float* d9, int invert, int n, const float* d_po
     if (n == 0) return 0;
     if (n < 0 || !d9 || !d_pose || !d_d9) return 1;
     return launch_pose_d9_bwd(d9, invert, n, d_pose, d_d9, (hipStream_t)stream);
+}
+
+// ---- pose evaluation (sparf_hip.h): S == 0 / n == 0 launch nothing, whatever the pointers; then the argument checks
+// joint_pose_nerf_trainer.py:290-311 evaluate_any_poses with :160-254 prealign_w2c_small_camera_systems and :257-287 evaluate_camera_alignment
+int sparf_pose_eval(const sparf_pose_eval_t* e, void* stream) {
+    if (!e) return 1;
+    if (e->S == 0) return 0;
+    if (e->S < 0 || e->B < 1 || e->B > SPARF_POSE_EVAL_MAX_POSES || (e->flags & ~SPARF_POSE_EVAL_ALIGN)) return 1;
+    if ((e->flags & SPARF_POSE_EVAL_ALIGN) && e->B < 2) return 1;
+    if (e->gt_sets != 1 && e->gt_sets != e->S) return 1;
+    if (!e->pose || !e->pose_gt || !e->stats || !e->errors || !e->aligned || !e->sim3 || !e->best) return 1;
+    return launch_pose_eval(e->pose, e->pose_gt, e->gt_sets, e->S, e->B, e->flags & SPARF_POSE_EVAL_ALIGN, e->stats, e->errors, e->aligned, e->sim3,
+                            e->best, e->scores, (hipStream_t)stream);
+}
+// align_trajectories.py:94-101 backtrack_from_aligning_the_trajectory
+int sparf_pose_backtrack(const float* pose_gt_w2c, int n, const float* sim3, int sim3_stride, float* out, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || sim3_stride < 0 || !pose_gt_w2c || !sim3 || !out) return 1;
+    return launch_pose_backtrack(pose_gt_w2c, n, sim3, sim3_stride, out, (hipStream_t)stream);
 }
 
 // ---- correspondence loss (sparf_hip.h): every argument check comes before any HIP call; n == 0 launches no kernel

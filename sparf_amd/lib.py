@@ -94,6 +94,17 @@ class ImageMetrics(ctypes.Structure):                   # include/sparf_hip.h sp
                 ("depth_scale", c_float), ("out", c_void_p), ("counts", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64)]
 
 
+class PoseEval(ctypes.Structure):                       # include/sparf_hip.h sparf_pose_eval_t
+    _fields_ = [("pose", c_void_p), ("pose_gt", c_void_p), ("gt_sets", c_int), ("S", c_int), ("B", c_int), ("flags", c_int),
+                ("stats", c_void_p), ("errors", c_void_p), ("aligned", c_void_p), ("sim3", c_void_p), ("best", c_void_p), ("scores", c_void_p)]
+
+
+POSE_EVAL_ALIGN = 1             # include/sparf_hip.h SPARF_POSE_EVAL_ALIGN
+POSE_EVAL_MAX_POSES = 64        # SPARF_POSE_EVAL_MAX_POSES
+POSE_EVAL_MAX_PAIRS = 90        # SPARF_POSE_EVAL_MAX_PAIRS
+POSE_EVAL_SIM3 = 13             # floats of a similarity: R (9, rows), t (3), s
+
+
 EXPORTS = {
     "sparf_abi_version": (c_int, []),
     "sparf_table_count": (c_int64, [c_int]),
@@ -128,6 +139,8 @@ EXPORTS = {
     "sparf_match_gather": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_int64] + [c_void_p] * 7),
     "sparf_image_metrics_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "sparf_image_metrics": (c_int, [POINTER(ImageMetrics), c_void_p]),
+    "sparf_pose_eval": (c_int, [POINTER(PoseEval), c_void_p]),
+    "sparf_pose_backtrack": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sparf_adam_workspace_floats": (c_int64, []),
     "sparf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p]),
