@@ -362,6 +362,48 @@ int sparf_match_gather(const int32_t* index, const int32_t* count, const int64_t
                        const float* corres, int64_t corres_channel_stride, const float* conf, float* pixels_self, int64_t* ray_self,
                        float* pixels_other, int64_t* ray_other, float* conf_out, void* stream);
 
+/* ---- DS-NeRF sparse depth loss ----------------------------------------------
+ * What SparseCOLMAPDepthLoss.compute_loss (source/training/core/base_losses.py:326-402) runs around
+ * its renders, as three calls over all B images.  No atomic; `count` is device memory, which the
+ * caller reads back once (the renders need the row counts on the host).
+ * sparf_colmap_compact replaces len(torch.where(colmap_depth > 0)[0]) of :367 and the B calls of
+ *   torch.where(colmap_depth_i > 1e-6) of :372: depth is colmap_depth [B][1][H][W] as stored
+ *   (float32, dense).  index[b][H W] (int32) receives the flat indices p = h W + w of the pixels
+ *   of image b with depth > 1e-6f in ascending (row-major) order, the order torch.where produces;
+ *   count[b] their number; count[B + b] the number of pixels of image b with depth > 0.0f.
+ * sparf_colmap_gather replaces the indexing by the permutation of :378-380, the two map gathers of
+ *   :382-383 and ray_idx of :386 for every image in one launch.  Image b holds
+ *   k_b = min(count[b], quota) rows; its row j is p = index[b][sel[b][j]] where count[b] > quota
+ *   (strictly: a count equal to the quota draws nothing, :377) and sel is given, else
+ *   p = index[b][j].  The rows of all images are packed in image order into K = sum k_b entries:
+ *   ray_idx (int64) = p, target = depth[b][p], weight = conf[b][p].  sel (int64 [B][quota], what
+ *   torch.randperm gives, cut to the quota; NULL: the first rows everywhere) is read only for the
+ *   images above the quota.  A position outside [0, count[b]) is the caller's error and is
+ *   clamped against the device count, and an index entry against H W, so that the launch stays
+ *   inside the allocations; no address depends on a value read from a map.
+ * sparf_colmap_loss replaces the weighted means of :391-398 and :400 over the packed rows, with
+ *   image boundaries from k_b = min(count[b], quota) (a caller with explicit row counts passes
+ *   them as count and quota = 2^30):
+ *   out[0] = (0.1 / B) sum_{b: k_b > 0} (1 / k_b) sum_j w_bj ((d_bj - p_bj)^2 [+ (d_bj - pf_bj)^2])
+ *   with B counting the skipped images too; d_depth[r] = (0.1 / B)(2 / k_b) w (p - d), likewise
+ *   d_depth_fine (either NULL ok).  Double arithmetic on the fp32 operands, sums in a fixed order
+ *   (thread, wave butterfly, waves, chunks in chunk order), one rounding per stored value: the
+ *   same bits from call to call.
+ * workspace: sparf_colmap_workspace_bytes(B, H W, rows) bytes, the larger of what a compaction of
+ *   B images of H W pixels and a loss of `rows` rows need (0 up to 4096 pixels / rows: one launch;
+ *   above, per-chunk counts / partial sums and two launches; NULL = the one-launch path at any size).
+ * Each returns 1 before any HIP call for a negative size, B <= 0 (or above 65535, the grid's y
+ * limit), H W or a row count above 2^30, quota < 0, K above B quota, or a missing required pointer;
+ * gather and loss return 0 without a launch, looking at no pointer, for K == 0 (out is then not
+ * written).  H W == 0 launches nothing and writes count = 0. */
+int64_t sparf_colmap_workspace_bytes(int B, int64_t n, int64_t rows);
+int sparf_colmap_compact(const float* depth, int B, int H, int W, int32_t* index, int32_t* count, void* workspace /*NULL ok*/, void* stream);
+int sparf_colmap_gather(const int32_t* index, const int32_t* count, const int64_t* sel /*NULL ok*/, int B, int H, int W, int quota, int K,
+                        const float* depth, const float* conf, int64_t* ray_idx, float* target, float* weight, void* stream);
+int sparf_colmap_loss(const float* target, const float* weight, const int32_t* count, int B, int quota, int K, const float* depth,
+                      const float* depth_fine /*NULL ok*/, float* out, float* d_depth /*NULL ok*/, float* d_depth_fine /*NULL ok*/,
+                      void* workspace /*NULL ok*/, void* stream);
+
 /* ---- evaluation metrics ----------------------------------------------------
  * compute_metrics / compute_metrics_masked / compute_depth_error (source/training/core/metrics.py:
  * 136-268, called per head by source/training/base.py:475-499 and nerf_trainer.py:387-405) with the

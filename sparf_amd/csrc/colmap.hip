@@ -1,0 +1,234 @@
+// DS-NeRF sparse depth loss: what SparseCOLMAPDepthLoss.compute_loss (base_losses.py:326-402) runs around its
+// renders -- per image a torch.where with a host readback, six index and gather operations and two weighted means, and one more
+// torch.where over all images -- as three calls: compact (the valid pixels of every image in torch.where's order, their number and the
+// number of positive pixels), gather (the selected rows of every image, packed in image order) and loss (the value and both gradient
+// seeds).  The logic of a pixel and of a row is colmap.h's; this file owns the ordered compaction, the gather, the sums and the entry points.
+//
+// Compaction: the scheme of matches.hip for a float map and B images at once; the image is the grid's y dimension.  It keeps row-major
+// order and uses no atomics: inside a wave a valid pixel's rank is the popcount of the wave64 ballot below its lane, the four waves'
+// totals go through LDS in wave order, and a running base is carried across tiles of COLMAP_BLOCK consecutive pixels.  Up to
+// COLMAP_CHUNK pixels one workgroup per image does all of it in one launch; above, a counts launch over chunks of COLMAP_CHUNK pixels
+// and a write launch in which each workgroup adds the counts of the chunks before it in chunk order.  No workgroup waits for another
+// inside a launch.  `count` stays in device memory; the host reads its 2 B ints once.
+// Gather: one thread per selected row; the maps are read in place.  Every address comes from the index list and the device counts --
+// clamped against the count and the image size -- and none from a value read out of a map.
+// Loss: double arithmetic on the fp32 operands, one rounding per stored value.  Sums follow photo.hip: a thread adds its rows in index
+// order, a wave its lanes by an xor butterfly, the waves in wave order, the chunks in chunk order: the same bits from call to call.
+#include <hip/hip_runtime.h>
+
+#include "../../include/sparf_hip.h"
+#include "colmap.h"
+
+namespace sparf {
+
+static constexpr int COLMAP_WAVES = COLMAP_BLOCK / 64;
+
+// the pixels [first, end) of one image in tiles of COLMAP_BLOCK, by one workgroup: -> base + the number valid, and pos + the number
+// positive (in every thread).  `write`: leave the indices; otherwise count only.
+static __device__ int colmap_compact_range(const float* depth, int32_t* index, int first, int end, int base, bool write, int& pos,
+                                           int (*wave_tot)[2]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int t0 = first; t0 < end; t0 += COLMAP_BLOCK) {
+        const int p = t0 + (int)threadIdx.x;
+        const float d = p < end ? depth[p] : 0.0f;
+        const bool flag = p < end && colmap_valid(d);
+        const unsigned long long ballot = __ballot(flag);
+        const unsigned long long ballot_pos = __ballot(p < end && colmap_positive(d));
+        if (lane == 0) {
+            wave_tot[wave][0] = __popcll(ballot);
+            wave_tot[wave][1] = __popcll(ballot_pos);
+        }
+        __syncthreads();
+        int off = base, total = 0;
+#pragma unroll
+        for (int w = 0; w < COLMAP_WAVES; ++w) {
+            const int c = wave_tot[w][0];
+            if (w < wave) off += c;
+            total += c;
+            pos += wave_tot[w][1];
+        }
+        if (write && flag) index[off + __popcll(ballot & ((1ull << lane) - 1ull))] = p;         // (rank < n: at most every pixel is valid)
+        base += total;
+        __syncthreads();                                 // wave_tot is written again by the next tile
+    }
+    return base;
+}
+
+// n <= COLMAP_CHUNK (or no workspace): one workgroup per image, every tile in turn
+__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_single_kernel(ColmapCompactArgs a) {
+    __shared__ int wave_tot[COLMAP_WAVES][2];
+    const int b = (int)blockIdx.y;
+    int pos = 0;
+    const int total = colmap_compact_range(a.depth + (size_t)b * (size_t)a.n, a.index + (size_t)b * (size_t)a.n, 0, a.n, 0, true, pos, wave_tot);
+    if (threadIdx.x == 0) {
+        a.count[b] = total;
+        a.count[a.B + b] = pos;
+    }
+}
+
+// n > COLMAP_CHUNK, one workgroup per chunk and image: the valid and the positive pixels of chunk c of image b at ws[b][c]
+__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_counts_kernel(ColmapCompactArgs a) {
+    __shared__ int wave_tot[COLMAP_WAVES][2];
+    const int b = (int)blockIdx.y, first = (int)blockIdx.x * COLMAP_CHUNK;
+    int pos = 0;
+    const int total = colmap_compact_range(a.depth + (size_t)b * (size_t)a.n, nullptr, first, min(a.n, first + COLMAP_CHUNK), 0, false, pos, wave_tot);
+    if (threadIdx.x == 0) {
+        int32_t* ws = a.ws + 2 * ((size_t)b * (size_t)a.chunks + blockIdx.x);
+        ws[0] = total;
+        ws[1] = pos;
+    }
+}
+
+// same grid: every workgroup adds the counts of the chunks before it in chunk order and writes its chunk; the last one of an image
+// leaves the image's two counts
+__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_write_kernel(ColmapCompactArgs a) {
+    __shared__ int wave_tot[COLMAP_WAVES][2];
+    const int b = (int)blockIdx.y, first = (int)blockIdx.x * COLMAP_CHUNK;
+    const int32_t* ws = a.ws + 2 * (size_t)b * (size_t)a.chunks;
+    int base = 0, pos = 0;
+    for (int c = 0; c < (int)blockIdx.x; ++c) {
+        base += ws[2 * c];
+        pos += ws[2 * c + 1];
+    }
+    const int total = colmap_compact_range(a.depth + (size_t)b * (size_t)a.n, a.index + (size_t)b * (size_t)a.n, first,
+                                           min(a.n, first + COLMAP_CHUNK), base, true, pos, wave_tot);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        a.count[b] = total;
+        a.count[a.B + b] = pos;
+    }
+}
+
+// base_losses.py:378-386 for row j of image b: the pixel behind the j-th selected entry of the image's index list, and what the two
+// maps hold there
+__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_gather_kernel(ColmapGatherArgs a) {
+    const int b = (int)blockIdx.y, j = (int)blockIdx.x * COLMAP_BLOCK + (int)threadIdx.x;
+    const int count = a.count[b];
+    if (j >= colmap_rows(count, a.quota)) return;
+    const int r = colmap_offset(a.count, b, a.quota) + j;
+    if (r >= a.K) return;                                // (the caller's K is the sum of the rows: never taken then)
+    const size_t image = (size_t)b * (size_t)a.n;
+    const int p = colmap_pixel_of_row(a.index + image, a.sel ? a.sel + (size_t)b * (size_t)a.quota : nullptr, count, a.quota, a.n, j);
+    a.ray_idx[r] = (int64_t)p;
+    a.target[r] = a.depth[image + (size_t)p];
+    a.weight[r] = a.conf[image + (size_t)p];
+}
+
+// the rows first, first + COLMAP_BLOCK, ... < end: -> the sum of their terms over k_b, their seeds stored
+static __device__ double colmap_loss_loop(const ColmapLossArgs& a, int first, int end) {
+    double acc = 0.0;
+    for (int r = first; r < end; r += COLMAP_BLOCK) {
+        int b, j, k;
+        if (!colmap_locate(a.count, a.B, a.quota, r, b, j, k)) {      // (a row past the images' rows: the caller's K is too large)
+            if (a.d_depth) a.d_depth[r] = 0.0f;
+            if (a.d_depth_fine) a.d_depth_fine[r] = 0.0f;
+            continue;
+        }
+        const double d = (double)a.target[r], w = (double)a.weight[r], p = (double)a.depth[r];
+        const double pf = a.depth_fine ? (double)a.depth_fine[r] : 0.0;
+        acc += colmap_row_term(d, w, p, a.depth_fine != nullptr, pf) / (double)k;
+        if (a.d_depth) a.d_depth[r] = (float)colmap_row_seed(d, w, p, k, a.B);
+        if (a.d_depth_fine) a.d_depth_fine[r] = (float)colmap_row_seed(d, w, pf, k, a.B);
+    }
+    return acc;
+}
+
+// the total of a workgroup, in every thread: wave butterfly, then the waves in order
+static __device__ double colmap_block_total(double v, double* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    double tot = red[0];
+#pragma unroll
+    for (int w = 1; w < COLMAP_WAVES; ++w) tot += red[w];
+    return tot;
+}
+
+// K <= COLMAP_CHUNK (or no workspace): one workgroup
+__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_loss_single_kernel(ColmapLossArgs a) {
+    __shared__ double red[COLMAP_WAVES];
+    const double tot = colmap_block_total(colmap_loss_loop(a, threadIdx.x, a.K), red);
+    if (threadIdx.x == 0) a.out[0] = (float)colmap_total(tot, a.B);
+}
+// K > COLMAP_CHUNK, one workgroup per chunk of rows: its total at ws[chunk]
+__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_loss_partial_kernel(ColmapLossArgs a) {
+    __shared__ double red[COLMAP_WAVES];
+    const int first = (int)blockIdx.x * COLMAP_CHUNK;
+    const double tot = colmap_block_total(colmap_loss_loop(a, first + (int)threadIdx.x, min(a.K, first + COLMAP_CHUNK)), red);
+    if (threadIdx.x == 0) a.ws[blockIdx.x] = tot;
+}
+// the partial totals added in chunk order
+__global__ void colmap_loss_finish_kernel(ColmapLossArgs a, int chunks) {
+    double tot = 0.0;
+    for (int c = 0; c < chunks; ++c) tot += a.ws[c];
+    a.out[0] = (float)colmap_total(tot, a.B);
+}
+
+static inline int64_t colmap_chunks(int64_t n) { return (n + COLMAP_CHUNK - 1) / COLMAP_CHUNK; }
+
+}  // namespace sparf
+
+using namespace sparf;
+
+// ---- the entry points (sparf_hip.h): every argument check comes before any HIP call
+static const int64_t kColmapMax = (int64_t)1 << 30;
+
+int64_t sparf_colmap_workspace_bytes(int B, int64_t n, int64_t rows) {
+    int64_t compact = 0, loss = 0;
+    if (B > 0 && B <= COLMAP_MAX_IMAGES && n > COLMAP_CHUNK && n <= kColmapMax) compact = (int64_t)B * colmap_chunks(n) * 2 * (int64_t)sizeof(int32_t);
+    if (rows > COLMAP_CHUNK && rows <= kColmapMax) loss = colmap_chunks(rows) * (int64_t)sizeof(double);
+    return compact > loss ? compact : loss;
+}
+
+int sparf_colmap_compact(const float* depth, int B, int H, int W, int32_t* index, int32_t* count, void* workspace, void* stream) {
+    if (B <= 0 || B > COLMAP_MAX_IMAGES || H < 0 || W < 0 || (int64_t)H * W > kColmapMax || !count) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int n = H * W;
+    if (n == 0) return hipMemsetAsync(count, 0, 2 * (size_t)B * sizeof(int32_t), s) == hipSuccess ? 0 : 2;      // (an empty tensor has no address)
+    if (!depth || !index) return 1;
+    ColmapCompactArgs a{};
+    a.depth = depth; a.B = B; a.n = n; a.chunks = (int)colmap_chunks(n); a.index = index; a.count = count; a.ws = (int32_t*)workspace;
+    if (n <= COLMAP_CHUNK || !a.ws) {
+        hipLaunchKernelGGL(colmap_compact_single_kernel, dim3(1, B), dim3(COLMAP_BLOCK), 0, s, a);
+        return hipGetLastError() == hipSuccess ? 0 : 2;
+    }
+    hipLaunchKernelGGL(colmap_compact_counts_kernel, dim3(a.chunks, B), dim3(COLMAP_BLOCK), 0, s, a);
+    if (hipGetLastError() != hipSuccess) return 2;
+    hipLaunchKernelGGL(colmap_compact_write_kernel, dim3(a.chunks, B), dim3(COLMAP_BLOCK), 0, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int sparf_colmap_gather(const int32_t* index, const int32_t* count, const int64_t* sel, int B, int H, int W, int quota, int K, const float* depth,
+                        const float* conf, int64_t* ray_idx, float* target, float* weight, void* stream) {
+    if (B <= 0 || B > COLMAP_MAX_IMAGES || H < 0 || W < 0 || (int64_t)H * W > kColmapMax || quota < 0 || K < 0 || (int64_t)K > kColmapMax) return 1;
+    if ((int64_t)K > (int64_t)B * quota || (int64_t)K > (int64_t)B * H * W) return 1;      // more rows than the images can hold
+    if (K == 0) return 0;
+    if (!index || !count || !depth || !conf || !ray_idx || !target || !weight) return 1;
+    ColmapGatherArgs a{};
+    a.index = index; a.count = count; a.sel = sel; a.B = B; a.n = H * W; a.quota = quota; a.K = K;
+    a.depth = depth; a.conf = conf; a.ray_idx = ray_idx; a.target = target; a.weight = weight;
+    const int per_image = quota < a.n ? quota : a.n;
+    hipLaunchKernelGGL(colmap_gather_kernel, dim3((per_image + COLMAP_BLOCK - 1) / COLMAP_BLOCK, B), dim3(COLMAP_BLOCK), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int sparf_colmap_loss(const float* target, const float* weight, const int32_t* count, int B, int quota, int K, const float* depth,
+                      const float* depth_fine, float* out, float* d_depth, float* d_depth_fine, void* workspace, void* stream) {
+    if (B <= 0 || B > COLMAP_MAX_IMAGES || quota < 0 || K < 0 || (int64_t)K > kColmapMax || (d_depth_fine && !depth_fine)) return 1;
+    if (K == 0) return 0;                                // nothing to launch, no pointer looked at: the loss of no rows is the caller's zero
+    if (!target || !weight || !count || !depth || !out) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    ColmapLossArgs a{};
+    a.target = target; a.weight = weight; a.count = count; a.B = B; a.quota = quota; a.K = K; a.depth = depth; a.depth_fine = depth_fine;
+    a.out = out; a.d_depth = d_depth; a.d_depth_fine = d_depth_fine; a.ws = (double*)workspace;
+    if (K <= COLMAP_CHUNK || !a.ws) {
+        hipLaunchKernelGGL(colmap_loss_single_kernel, dim3(1), dim3(COLMAP_BLOCK), 0, s, a);
+        return hipGetLastError() == hipSuccess ? 0 : 2;
+    }
+    const int chunks = (int)colmap_chunks(K);
+    hipLaunchKernelGGL(colmap_loss_partial_kernel, dim3(chunks), dim3(COLMAP_BLOCK), 0, s, a);
+    if (hipGetLastError() != hipSuccess) return 2;
+    hipLaunchKernelGGL(colmap_loss_finish_kernel, dim3(1), dim3(1), 0, s, a, chunks);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}

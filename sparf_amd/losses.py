@@ -1,5 +1,5 @@
 """The correspondence loss and, below it, the depth-consistency loss, the photometric, mask and
-depth-patch loss and the correspondence sampler.
+depth-patch loss, the correspondence sampler and the DS-NeRF sparse depth loss.
 
 The correspondence loss: SPARF's re-projection of rendered depth at matched pixels through the current relative
 pose (corres_loss.py:50-95, :183-219; batched_geometry_utils.py:199-228; base_losses.py:197-224).
@@ -24,7 +24,13 @@ The correspondence sampler (base_corres_loss.py:260-269, :323-
 an ordered compaction of the valid-correspondence mask (ops.match_compact), one readback of the count, torch.randperm as the reference
 calls it, and one gather of the selected rows (ops.match_gather); `install_sampler()` puts the three methods that hold those lines under
 the reference's names.
+
+The DS-NeRF sparse depth loss (base_losses.py:326-402) is `sparse_depth_select` -- one ordered compaction of the
+valid pixels of every COLMAP map (ops.colmap_compact), one readback of the 2 B counts, torch.randperm as the reference calls it, a
+gather of the selected rows (ops.colmap_gather) -- and `sparse_depth_loss` (ops.ColmapLoss: the value and both seeds in one call);
+`install_colmap_depth()` puts a method under the reference's name that issues every render before it reads any.
 """
+import collections
 import contextlib
 
 import torch
@@ -833,3 +839,234 @@ def uninstall_sampler():
         else:
             delattr(obj, name)
     _original_sampler.clear()
+
+
+# ================================================================================================ the DS-NeRF sparse depth loss
+# SparseCOLMAPDepthLoss.compute_loss (base_losses.py:326-402), the loss of the DS-NeRF baseline trainer and of the
+# joint trainer under load_colmap_depth.  The reference runs, per image, a torch.where with a host readback, a randperm, six index and
+# gather operations, a render of its own whose depth it reads at once, and two weighted means -- B + 1 readbacks and B small renders.
+# Here: `sparse_depth_select` (ops.colmap_compact over all images, ONE readback of the 2 B counts, torch.randperm as the reference calls
+# it, ops.colmap_gather) and `sparse_depth_loss` (ops.ColmapLoss, one call for the value and both seeds); `install_colmap_depth()` puts
+# a method under the reference's name that issues every render before it reads any, so that deferred renders run as one batch.
+COLMAP_METHOD = "compute_loss"
+SparseCounts = collections.namedtuple("SparseCounts", "valid positive rows quota device")
+SparseCounts.__doc__ = """what sparse_depth_select read back: per image the valid pixels (depth > 1e-6), the positive pixels (depth > 0) and the
+rows selected, min(valid, quota), as Python ints; `device`: the int32 [2 B] tensor the ints were read from (None on the torch route)"""
+
+
+def _colmap_takes_kernel(*maps):
+    return _takes_kernel((), maps) and all(m.dtype == torch.float32 for m in maps)
+
+
+def _zero_loss(device):
+    return torch.tensor(0., requires_grad=True).to(device)       # base_losses.py:356
+
+
+# ---------------------------------------------------------------------------------------------- the torch restatement
+def sparse_depth_select_torch(colmap_depth, colmap_conf, rand_rays, perms=None):
+    """base_losses.py:363-386 without the renders, in the reference's operation order; arguments and results as sparse_depth_select"""
+    H, W = colmap_depth.shape[-2:]
+    depth, conf = colmap_depth.detach().reshape(-1, H, W), colmap_conf.detach().reshape(-1, H, W)
+    B, dev = depth.shape[0], depth.device
+    quota = rand_rays // B
+    perc = len(torch.where(depth > 0)[0]) / depth.nelement()
+    positive = [int((depth[b] > 0).sum()) for b in range(B)]
+    rays, targets, weights, valid = [], [], [], []
+    for b in range(B):
+        h, w = torch.where(depth[b] > 1e-6)
+        valid.append(len(h))
+        if len(h) > quota:
+            random = (perms[b] if perms is not None and perms[b] is not None else torch.randperm(len(h), device=dev))[:quota]
+            h, w = h[random], w[random]
+        rays.append(h * W + w)
+        targets.append(depth[b][h, w].reshape(-1))
+        weights.append(conf[b][h, w].reshape(-1))
+    counts = SparseCounts(valid, positive, [min(v, quota) for v in valid], quota, None)
+    return rays, torch.cat(targets), torch.cat(weights), counts, perc
+
+
+def _rows_of(counts_or_rows):
+    return list(counts_or_rows.rows) if isinstance(counts_or_rows, SparseCounts) else [int(k) for k in counts_or_rows]
+
+
+def sparse_depth_loss_torch(target, weight, counts_or_rows, depths, depths_fine=None, batch_size=None):
+    """base_losses.py:391-400 on the packed rows, with out-of-place adds (the reference's `loss += ...` on a leaf cannot run under
+    autograd on CPU tensors); arguments and result as sparse_depth_loss"""
+    rows = _rows_of(counts_or_rows)
+    batch_size = len(rows) if batch_size is None else batch_size
+    kept = [k for k in rows if k > 0]
+    if len(depths) != len(kept) or (depths_fine is not None and len(depths_fine) != len(kept)):
+        raise ValueError(f"sparse_depth_loss: {len(depths)} rendered depths for {len(kept)} images with rows")
+    if not kept:
+        return _zero_loss(target.device)
+    loss, off = 0, 0
+    for i, k in enumerate(kept):
+        t, w = target[off:off + k], weight[off:off + k]
+        loss = loss + torch.mean(((t - depths[i].reshape(-1)) ** 2) * w)
+        if depths_fine is not None:
+            loss = loss + torch.mean(((t - depths_fine[i].reshape(-1)) ** 2) * w)
+        off += k
+    return 0.1 * loss / batch_size
+
+
+# ---------------------------------------------------------------------------------------------- the public functions
+def _split(t, rows):
+    return list(torch.split(t, rows))
+
+
+def sparse_depth_select(colmap_depth, colmap_conf, rand_rays, perms=None):
+    """The rays a DS-NeRF iteration renders: per image of colmap_depth [B,1,H,W] the pixels with depth > 1e-6 in row-major order; where an
+    image has MORE than quota = rand_rays // B of them, the rows perm[:quota] of them, with perm = torch.randperm(count, device=...) drawn
+    per image in image order when `perms` (a list per image, entries None for no permutation) gives none: the reference's own calls, so
+    the same seed draws the same rays and leaves the generator in the same state.  The maps are read in place.
+    -> (ray_idx: a list of B int64 tensors, flat indices h W + w, empty for an image without valid pixels; target [K] and weight [K]
+    float32, the two maps at those pixels packed in image order; counts: a SparseCounts, the ONE readback; perc_col_depth: the share of
+    pixels with depth > 0, a Python float, the reference's division)."""
+    if not _colmap_takes_kernel(colmap_depth, colmap_conf):
+        return sparse_depth_select_torch(colmap_depth, colmap_conf, rand_rays, perms)
+    B, (H, W) = colmap_depth.shape[0], colmap_depth.shape[-2:]
+    quota = rand_rays // B
+    index, count = ops.colmap_compact(colmap_depth)
+    counts, perc = _read_counts(count, B, H * W, quota)
+    K = sum(counts.rows)
+    sel = None
+    for b in range(B):
+        if counts.valid[b] > quota:
+            perm = perms[b] if perms is not None and perms[b] is not None else torch.randperm(counts.valid[b], device=colmap_depth.device)
+            if sel is None:
+                sel = torch.zeros(B, quota, device=colmap_depth.device, dtype=torch.int64)
+            sel[b].copy_(perm[:quota])
+    ray_idx, target, weight = ops.colmap_gather(index, count, sel, quota, K, H, W, colmap_depth, colmap_conf)
+    return _split(ray_idx, counts.rows), target, weight, counts, perc
+
+
+def _read_counts(count, B, n, quota):
+    """the one readback: the 2 B ints of ops.colmap_compact -> (SparseCounts, perc_col_depth as base_losses.py:367 divides it)"""
+    both = count.tolist()
+    valid, positive = both[:B], both[B:]
+    return SparseCounts(valid, positive, [min(v, quota) for v in valid], quota, count), sum(positive) / (B * n)
+
+
+def sparse_depth_loss(target, weight, counts_or_rows, depths, depths_fine=None, batch_size=None):
+    """The DS-NeRF depth loss of the selected rows: target / weight [K] as sparse_depth_select packs them; counts_or_rows its SparseCounts,
+    or the rows per image as ints (zeros included); depths / depths_fine: the rendered depths of the images WITH rows, in image order,
+    k_b elements each in any shape.  batch_size (default: the number of images) divides the sum, skipped images counted, as
+    base_losses.py:400 does.  L = (0.1 / B) sum_b (1 / k_b) sum_j w ((d - p)^2 [+ (d - pf)^2]); gradients go to the rendered depths.
+    -> a 0-dim tensor; with no rows at all the zero loss with requires_grad, and no launch."""
+    rows = _rows_of(counts_or_rows)
+    batch_size = len(rows) if batch_size is None else batch_size
+    depths = list(depths)
+    depths_fine = list(depths_fine) if depths_fine is not None else None
+    values = depths + (depths_fine or [])
+    if not values or not _takes_kernel(values, (target, weight)) or target.dtype != torch.float32 or weight.dtype != torch.float32:
+        return sparse_depth_loss_torch(target, weight, rows, depths, depths_fine, batch_size)
+    kept = [k for k in rows if k > 0]
+    if len(depths) != len(kept) or (depths_fine is not None and len(depths_fine) != len(kept)):
+        raise ValueError(f"sparse_depth_loss: {len(depths)} rendered depths for {len(kept)} images with rows")
+    if isinstance(counts_or_rows, SparseCounts) and counts_or_rows.device is not None:
+        count, quota = counts_or_rows.device, counts_or_rows.quota
+    else:
+        count, quota = torch.tensor(rows, dtype=torch.int32).to(target.device), ops.COLMAP_ALL_ROWS
+    return ops.ColmapLoss.apply(target, weight, count, quota, batch_size, len(depths), *values)
+
+
+def _render_rays(self, data_dict, pose, intr, H, W, iteration, b, ray_idx):
+    return self.net.render_image_at_specific_pose_and_rays(self.opt, data_dict, pose[b], intr[b], H, W, ray_idx=ray_idx, mode='train',
+                                                           iter=iteration)
+
+
+def _colmap_loop_torch(self, opt, data_dict, pose, intr, H, W, iteration):
+    """base_losses.py:363-400, the reference's loop in its own order -- per image the selection, the randperm and the render -- except
+    that no result is read before every call is made, and that the adds are out of place.  -> (loss, perc_col_depth)"""
+    depth, conf = data_dict.colmap_depth.view(-1, H, W), data_dict.colmap_conf.view(-1, H, W)
+    B = pose.shape[0]
+    quota = opt.nerf.rand_rays // B
+    perc = len(torch.where(depth > 0)[0]) / depth.nelement()
+    rets, targets, weights, rows = [], [], [], []
+    for b in range(B):
+        h, w = torch.where(depth[b] > 1e-6)
+        if len(h) == 0:
+            rows.append(0)
+            continue
+        if len(h) > quota:
+            random = torch.randperm(len(h), device=self.device)[:quota]
+            h, w = h[random], w[random]
+        rows.append(len(h))
+        targets.append(depth[b][h, w].reshape(-1))
+        weights.append(conf[b][h, w].reshape(-1))
+        rets.append(_render_rays(self, data_dict, pose, intr, H, W, iteration, b, h * W + w))
+    if not rets:
+        return _zero_loss(self.device), perc
+    fine = 'depth_fine' in rets[0].keys()
+    return sparse_depth_loss_torch(torch.cat(targets), torch.cat(weights), rows, [r.depth for r in rets],
+                                   [r.depth_fine for r in rets] if fine else None, B), perc
+
+
+def compute_colmap_depth_loss(self, opt, data_dict, output_dict, iteration, mode=None, plot=False, **kwargs):
+    """The method of SparseCOLMAPDepthLoss (base_losses.py:335-402) under its own signature and return convention: reads
+    opt.nerf.rand_rays, data_dict.colmap_depth / colmap_conf [B,1,H,W], image and intr, and calls self.net.get_w2c_pose and, per image with
+    a valid pixel, self.net.render_image_at_specific_pose_and_rays as :387 does.  One compaction of all images, ONE readback of the 2 B
+    counts; then image by image its randperm (if the reference draws one) and its render call, in the reference's order, so that the
+    generators see the reference's sequence; no result is read before every call is made, so deferred renders (opt.hip.lazy_batch) run
+    as one batch.  A gather launch covers the images from one that draws up to the next that draws: the rows of an image are on the
+    device before its render is called, and no permutation is drawn ahead of a render the reference makes first."""
+    from .edict import EasyDict as edict
+    if mode != 'train':
+        return {}, {}, {}
+    H, W = data_dict.image.shape[-2:]
+    pose = self.net.get_w2c_pose(opt, data_dict, mode=mode)
+    intr = data_dict.intr
+    colmap_depth, colmap_conf = data_dict.colmap_depth, data_dict.colmap_conf
+    B = pose.shape[0]
+    if not _colmap_takes_kernel(colmap_depth, colmap_conf):
+        loss, perc = _colmap_loop_torch(self, opt, data_dict, pose, intr, H, W, iteration)
+        return edict(colmap_depth=loss), {'perc_col_depth': perc}, {}
+    quota = opt.nerf.rand_rays // B
+    index, count = ops.colmap_compact(colmap_depth)
+    counts, perc = _read_counts(count, B, H * W, quota)                  # the one readback
+    stats_dict = {'perc_col_depth': perc}
+    rows, K = counts.rows, sum(counts.rows)
+    if K == 0:
+        return edict(colmap_depth=_zero_loss(self.device)), stats_dict, {}
+    dev = colmap_depth.device
+    outs = (torch.empty(K, device=dev, dtype=torch.int64), torch.empty(K, device=dev, dtype=torch.float32),
+            torch.empty(K, device=dev, dtype=torch.float32))
+    offs = [0]
+    for k in rows:
+        offs.append(offs[-1] + k)
+    draws = [b for b in range(B) if counts.valid[b] > quota]
+    gathered, rets = 0, []
+    for b in range(B):
+        if rows[b] == 0:
+            continue
+        if b >= gathered:
+            sel = torch.randperm(counts.valid[b], device=self.device)[:quota] if counts.valid[b] > quota else None
+            gathered = next((d for d in draws if d > b), B)
+            ops.colmap_gather(index, count, sel, quota, offs[gathered] - offs[b], H, W, colmap_depth, colmap_conf, images=(b, gathered),
+                              outs=tuple(o[offs[b]:offs[gathered]] for o in outs))
+        rets.append(_render_rays(self, data_dict, pose, intr, H, W, iteration, b, outs[0][offs[b]:offs[b + 1]]))
+    fine = 'depth_fine' in rets[0].keys()                                 # the first read: the deferred renders launch here, as one batch
+    loss = sparse_depth_loss(outs[1], outs[2], counts, [r.depth for r in rets], [r.depth_fine for r in rets] if fine else None, batch_size=B)
+    return edict(colmap_depth=loss), stats_dict, {}
+
+
+_patched_colmap = []
+
+
+def install_colmap_depth(base_losses_module):
+    """Opt-in, and independent of the other installs: put compute_colmap_depth_loss on `base_losses_module.SparseCOLMAPDepthLoss` under
+    the name compute_loss until `uninstall_colmap_depth()`.  Nothing in this package calls it."""
+    if _patched_colmap:
+        raise RuntimeError("sparf_amd.losses.install_colmap_depth: already installed; call uninstall_colmap_depth() first")
+    cls = base_losses_module.SparseCOLMAPDepthLoss
+    _patched_colmap.append((cls, COLMAP_METHOD, COLMAP_METHOD in vars(cls), vars(cls).get(COLMAP_METHOD)))
+    setattr(cls, COLMAP_METHOD, compute_colmap_depth_loss)
+
+
+def uninstall_colmap_depth():
+    while _patched_colmap:
+        obj, name, own, old = _patched_colmap.pop()
+        if own:
+            setattr(obj, name, old)
+        else:
+            delattr(obj, name)

@@ -1140,6 +1140,150 @@ def match_gather(index, count, sel, k, H, W, corres, conf):
     return outs
 
 
+# ---------------------------------------------------------------------------------------------- DS-NeRF sparse depth loss
+# SparseCOLMAPDepthLoss.compute_loss (base_losses.py:326-402) around its renders.  The selection carries no gradient;
+# the loss gives one to the rendered depths only.
+COLMAP_ALL_ROWS = 1 << 30                                   # a quota that cuts nothing: `count` then holds the row counts themselves
+
+
+def _colmap_map(t, what):
+    """a COLMAP map [B,1,H,W] (or [B,H,W]) float32 -> (dense [B, H W] view of its own storage, B, H, W); only another layout is copied"""
+    if t.dtype != torch.float32 or t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[1] != 1):
+        raise ValueError(f"sparse depth loss: {what} must be float32 [B,1,H,W] or [B,H,W], got {t.dtype} {list(t.shape)}")
+    B, (H, W) = t.shape[0], t.shape[-2:]
+    d = t.detach()
+    d = d if d.is_contiguous() else d.contiguous()
+    return d.view(B, H * W), B, H, W
+
+
+def colmap_compact(colmap_depth):
+    """sparf_colmap_compact over the B images of colmap_depth [B,1,H,W] (read in place) -> (index [B, H W] int32 whose first count[b]
+    entries of row b are the flat indices of the pixels of image b with depth > 1e-6 in row-major order, count [2 B] int32: those
+    numbers, then the numbers of pixels with depth > 0), both on the device: no readback"""
+    d, B, H, W = _colmap_map(colmap_depth, "colmap_depth")
+    if B == 0:
+        raise ValueError("sparse depth loss: no image")
+    dev = d.device
+    L.require_gpu(dev)
+    n = H * W
+    index = torch.empty(B, n, device=dev, dtype=torch.int32)
+    count = torch.empty(2 * B, device=dev, dtype=torch.int32)
+    lib = L.load()
+    nb = int(lib.sparf_colmap_workspace_bytes(B, n, 0))
+    ws = torch.empty(nb // 4, device=dev, dtype=torch.int32) if nb else None
+    p = L.ptr
+    with L.on(dev):
+        L.check(lib.sparf_colmap_compact(p(d), B, H, W, p(index), p(count), p(ws), L.stream_ptr(dev)), "sparf_colmap_compact")
+    return index, count
+
+
+def colmap_gather(index, count, sel, quota, K, H, W, colmap_depth, colmap_conf, images=None, outs=None):
+    """sparf_colmap_gather: the K = sum_b min(count[b], quota) selected rows of the images [b0, b1) (`images`; None: all of them), packed
+    in image order.  sel: int64 [b1 - b0, quota] positions in each image's index row, read for the images with count[b] > quota (a
+    single [quota] row serves a range whose FIRST image is the only one above the quota), or None: the first rows everywhere.
+    outs: (ray_idx, target, weight) dense [K] tensors to fill, or None: new ones.
+    -> (ray_idx [K] int64, target [K] float32, weight [K] float32).  K == 0: no call."""
+    dev = index.device
+    K, quota = int(K), int(quota)
+    if outs is None:
+        outs = (torch.empty(K, device=dev, dtype=torch.int64), torch.empty(K, device=dev, dtype=torch.float32),
+                torch.empty(K, device=dev, dtype=torch.float32))
+    if K == 0:
+        return outs
+    L.require_gpu(dev)
+    d, B, _, _ = _colmap_map(colmap_depth, "colmap_depth")
+    c, Bc, Hc, Wc = _colmap_map(colmap_conf, "colmap_conf")
+    if (Bc, Hc, Wc) != (B, H, W) or tuple(index.shape) != (B, H * W):
+        raise ValueError("sparse depth loss: colmap_depth, colmap_conf and the index list are of different sizes")
+    b0, b1 = (0, B) if images is None else images
+    if not 0 <= b0 < b1 <= B:
+        raise ValueError(f"sparse depth loss: images {images} of {B}")
+    if sel is not None:
+        if sel.dtype != torch.int64 or sel.numel() not in (quota, (b1 - b0) * quota):
+            raise ValueError(f"sparse depth loss: the selection must be int64 [{b1 - b0}, {quota}] or [{quota}], got {sel.dtype} {list(sel.shape)}")
+        sel = sel.detach().reshape(-1).contiguous()
+    if any(o.numel() != K for o in outs):
+        raise ValueError(f"sparse depth loss: the outputs must hold {K} rows")
+    lib = L.load()
+    p = L.ptr
+    with L.on(dev):
+        L.check(lib.sparf_colmap_gather(p(index[b0:b1]), p(count[b0:b1]), p(sel), b1 - b0, H, W, quota, K, p(d[b0:b1]), p(c[b0:b1]), *map(p, outs),
+                                        L.stream_ptr(dev)), "sparf_colmap_gather")
+    return outs
+
+
+def _adjacent(ts):
+    """whether the dense float32 tensors `ts` lie one behind the other in one storage (the rendered depths of one pass buffer)"""
+    for a, b in zip(ts, ts[1:]):
+        if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr() or a.data_ptr() + 4 * a.numel() != b.data_ptr():
+            return False
+    return True
+
+
+def _colmap_packed(ts, K):
+    """the rendered depths of the images as one dense [K] float32 tensor: read in place where they are adjacent views of one buffer,
+    one torch.cat otherwise"""
+    ts = [t.detach() for t in ts]
+    if all(t.dtype == torch.float32 and t.is_contiguous() for t in ts) and (len(ts) == 1 or _adjacent(ts)):
+        return torch.as_strided(ts[0], (K,), (1,))
+    return torch.cat([t.reshape(-1).to(torch.float32) for t in ts])
+
+
+class ColmapLoss(torch.autograd.Function):
+    """base_losses.py:391-400 over the packed rows of every rendered image in one library call, which also leaves the gradient seeds of
+    the rendered depths; the backward multiplies them by the upstream scalar and makes no call.  count: int32 on the device, image b
+    holds min(count[b], quota) rows; nd depths (any shape, one per image with rows, in image order), then none or nd fine depths.
+    -> the loss, a 0-dim tensor"""
+
+    @staticmethod
+    def forward(ctx, target, weight, count, quota, batch_size, nd, *depths):
+        op = "sparse depth loss"
+        dev = target.device
+        L.require_gpu(dev)
+        nd, B, quota = int(nd), int(batch_size), int(quota)
+        if len(depths) not in (nd, 2 * nd) or nd == 0:
+            raise ValueError(f"{op}: {len(depths)} depth tensors for {nd} rendered images")
+        coarse, fine = depths[:nd], depths[nd:]
+        K = target.numel()
+        if sum(t.numel() for t in coarse) != K or (fine and [t.numel() for t in fine] != [t.numel() for t in coarse]):
+            raise ValueError(f"{op}: the rendered depths do not hold the {K} selected rows")
+        if count.dtype != torch.int32 or count.numel() < B:
+            raise ValueError(f"{op}: the counts must be int32 [{B}] on the device")
+        t, w = _flat(target, K, "target", op, "rows"), _flat(weight, K, "weight", op, "rows")
+        p_c = _colmap_packed(coarse, K)
+        p_f = _colmap_packed(fine, K) if fine else None
+        out = torch.empty(1, device=dev, dtype=torch.float32)
+        need_c, need_f = any(ctx.needs_input_grad[6:6 + nd]), any(ctx.needs_input_grad[6 + nd:])
+        s_c = torch.empty(K, device=dev, dtype=torch.float32) if need_c else None
+        s_f = torch.empty(K, device=dev, dtype=torch.float32) if need_f else None
+        lib = L.load()
+        nb = int(lib.sparf_colmap_workspace_bytes(0, 0, K))
+        ws = torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None
+        p = L.ptr
+        with L.on(dev):
+            L.check(lib.sparf_colmap_loss(p(t), p(w), p(count.detach().contiguous()), B, quota, K, p(p_c), p(p_f), p(out), p(s_c), p(s_f), p(ws),
+                                          L.stream_ptr(dev)), "sparf_colmap_loss")
+        ctx.save_for_backward(s_c, s_f)
+        ctx.shapes = [d.shape for d in depths]
+        ctx.nd = nd
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        s_c, s_f = ctx.saved_tensors
+        grads = []
+        for s, shapes in ((s_c, ctx.shapes[:ctx.nd]), (s_f, ctx.shapes[ctx.nd:])):
+            if s is None:
+                grads += [None] * len(shapes)
+                continue
+            sg, off = s * g, 0
+            for shape in shapes:
+                grads.append(sg[off:off + shape.numel()].view(shape))
+                off += shape.numel()
+        return (None,) * 6 + tuple(grads)
+
+
 # ---------------------------------------------------------------------------------------------- evaluation metrics
 # SURVEY 8f next-10.  A plain function: evaluation carries no gradient.
 METRICS_OUTS = ("mse", "psnr", "ssim", "mse_masked", "psnr_masked", "ssim_masked", "abs_e", "rmse", "abs_e_scaled", "rmse_scaled")     # csrc/metrics.h
