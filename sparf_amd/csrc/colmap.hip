@@ -4,78 +4,66 @@
 // number of positive pixels), gather (the selected rows of every image, packed in image order) and loss (the value and both gradient
 // seeds).  The logic of a pixel and of a row is colmap.h's; this file owns the ordered compaction, the gather, the sums and the entry points.
 //
-// Compaction: the scheme of matches.hip for a float map and B images at once; the image is the grid's y dimension.  It keeps row-major
-// order and uses no atomics: inside a wave a valid pixel's rank is the popcount of the wave64 ballot below its lane, the four waves'
-// totals go through LDS in wave order, and a running base is carried across tiles of COLMAP_BLOCK consecutive pixels.  Up to
+// Compaction: B images at once, the image is the grid's y dimension.  It keeps row-major order and uses no atomics (ordered.h:
+// ordered_compact_range, in tiles of COLMAP_BLOCK consecutive pixels, with the positive pixels as a second, counted flag).  Up to
 // COLMAP_CHUNK pixels one workgroup per image does all of it in one launch; above, a counts launch over chunks of COLMAP_CHUNK pixels
-// and a write launch in which each workgroup adds the counts of the chunks before it in chunk order.  No workgroup waits for another
-// inside a launch.  `count` stays in device memory; the host reads its 2 B ints once.
+// and a write launch in which each workgroup adds the counts of the chunks before it in chunk order.  `count` stays in device memory;
+// the host reads its 2 B ints once.
 // Gather: one thread per selected row; the maps are read in place.  Every address comes from the index list and the device counts --
 // clamped against the count and the image size -- and none from a value read out of a map.
-// Loss: double arithmetic on the fp32 operands, one rounding per stored value.  Sums follow photo.hip: a thread adds its rows in index
-// order, a wave its lanes by an xor butterfly, the waves in wave order, the chunks in chunk order: the same bits from call to call.
+// Loss: double arithmetic on the fp32 operands, one rounding per stored value.  Sums are fixed-order (ordered.h: block_totals,
+// sum_parts): a thread adds its rows in index order, then the wave, the waves and the chunks in their order: the same bits from call to call.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sparf_hip.h"
 #include "colmap.h"
+#include "ordered.h"
 
 namespace sparf {
 
 static constexpr int COLMAP_WAVES = COLMAP_BLOCK / 64;
 
-// the pixels [first, end) of one image in tiles of COLMAP_BLOCK, by one workgroup: -> base + the number valid, and pos + the number
-// positive (in every thread).  `write`: leave the indices; otherwise count only.
-static __device__ int colmap_compact_range(const float* depth, int32_t* index, int first, int end, int base, bool write, int& pos,
-                                           int (*wave_tot)[2]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int t0 = first; t0 < end; t0 += COLMAP_BLOCK) {
-        const int p = t0 + (int)threadIdx.x;
-        const float d = p < end ? depth[p] : 0.0f;
-        const bool flag = p < end && colmap_valid(d);
-        const unsigned long long ballot = __ballot(flag);
-        const unsigned long long ballot_pos = __ballot(p < end && colmap_positive(d));
-        if (lane == 0) {
-            wave_tot[wave][0] = __popcll(ballot);
-            wave_tot[wave][1] = __popcll(ballot_pos);
-        }
-        __syncthreads();
-        int off = base, total = 0;
-#pragma unroll
-        for (int w = 0; w < COLMAP_WAVES; ++w) {
-            const int c = wave_tot[w][0];
-            if (w < wave) off += c;
-            total += c;
-            pos += wave_tot[w][1];
-        }
-        if (write && flag) index[off + __popcll(ballot & ((1ull << lane) - 1ull))] = p;         // (rank < n: at most every pixel is valid)
-        base += total;
-        __syncthreads();                                 // wave_tot is written again by the next tile
+// what is compacted (the item of ordered_compact_range): the valid pixels of image b, their flat indices as the rows; the positive
+// pixels are counted along.  run[] = {valid, positive}.
+struct ColmapItem {
+    const float* depth;
+    int32_t* index;
+    __device__ ColmapItem(const ColmapCompactArgs& a, int b) : depth(a.depth + (size_t)b * (size_t)a.n), index(a.index + (size_t)b * (size_t)a.n) {}
+    __device__ void flags(int p, bool in, bool (&f)[2]) const {
+        const float d = in ? depth[p] : 0.0f;            // one guarded read for both flags
+        f[0] = in & colmap_valid(d);
+        f[1] = in & colmap_positive(d);
     }
-    return base;
+    __device__ void place(int p, int j) const { index[j] = p; }
+    __device__ void mark(int, int) const {}
+};
+
+static __device__ void colmap_counts(const ColmapCompactArgs& a, int b, const int (&run)[2]) {
+    a.count[b] = run[0];
+    a.count[a.B + b] = run[1];
 }
 
 // n <= COLMAP_CHUNK (or no workspace): one workgroup per image, every tile in turn
 __global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_single_kernel(ColmapCompactArgs a) {
     __shared__ int wave_tot[COLMAP_WAVES][2];
     const int b = (int)blockIdx.y;
-    int pos = 0;
-    const int total = colmap_compact_range(a.depth + (size_t)b * (size_t)a.n, a.index + (size_t)b * (size_t)a.n, 0, a.n, 0, true, pos, wave_tot);
-    if (threadIdx.x == 0) {
-        a.count[b] = total;
-        a.count[a.B + b] = pos;
-    }
+    ColmapItem item(a, b);
+    int run[2] = {0, 0};
+    ordered_compact_range<COLMAP_BLOCK>(item, 0, a.n, true, run, wave_tot);
+    if (threadIdx.x == 0) colmap_counts(a, b, run);
 }
 
 // n > COLMAP_CHUNK, one workgroup per chunk and image: the valid and the positive pixels of chunk c of image b at ws[b][c]
 __global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_counts_kernel(ColmapCompactArgs a) {
     __shared__ int wave_tot[COLMAP_WAVES][2];
     const int b = (int)blockIdx.y, first = (int)blockIdx.x * COLMAP_CHUNK;
-    int pos = 0;
-    const int total = colmap_compact_range(a.depth + (size_t)b * (size_t)a.n, nullptr, first, min(a.n, first + COLMAP_CHUNK), 0, false, pos, wave_tot);
+    ColmapItem item(a, b);
+    int run[2] = {0, 0};
+    ordered_compact_range<COLMAP_BLOCK>(item, first, min(a.n, first + COLMAP_CHUNK), false, run, wave_tot);
     if (threadIdx.x == 0) {
         int32_t* ws = a.ws + 2 * ((size_t)b * (size_t)a.chunks + blockIdx.x);
-        ws[0] = total;
-        ws[1] = pos;
+        ws[0] = run[0];
+        ws[1] = run[1];
     }
 }
 
@@ -85,17 +73,15 @@ __global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_write_kernel(Colm
     __shared__ int wave_tot[COLMAP_WAVES][2];
     const int b = (int)blockIdx.y, first = (int)blockIdx.x * COLMAP_CHUNK;
     const int32_t* ws = a.ws + 2 * (size_t)b * (size_t)a.chunks;
+    ColmapItem item(a, b);
     int base = 0, pos = 0;
     for (int c = 0; c < (int)blockIdx.x; ++c) {
         base += ws[2 * c];
         pos += ws[2 * c + 1];
     }
-    const int total = colmap_compact_range(a.depth + (size_t)b * (size_t)a.n, a.index + (size_t)b * (size_t)a.n, first,
-                                           min(a.n, first + COLMAP_CHUNK), base, true, pos, wave_tot);
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        a.count[b] = total;
-        a.count[a.B + b] = pos;
-    }
+    int run[2] = {base, pos};
+    ordered_compact_range<COLMAP_BLOCK>(item, first, min(a.n, first + COLMAP_CHUNK), true, run, wave_tot);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) colmap_counts(a, b, run);
 }
 
 // base_losses.py:378-386 for row j of image b: the pixel behind the j-th selected entry of the image's index list, and what the two
@@ -132,36 +118,27 @@ static __device__ double colmap_loss_loop(const ColmapLossArgs& a, int first, in
     return acc;
 }
 
-// the total of a workgroup, in every thread: wave butterfly, then the waves in order
-static __device__ double colmap_block_total(double v, double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double tot = red[0];
-#pragma unroll
-    for (int w = 1; w < COLMAP_WAVES; ++w) tot += red[w];
-    return tot;
-}
-
 // K <= COLMAP_CHUNK (or no workspace): one workgroup
 __global__ void __launch_bounds__(COLMAP_BLOCK) colmap_loss_single_kernel(ColmapLossArgs a) {
-    __shared__ double red[COLMAP_WAVES];
-    const double tot = colmap_block_total(colmap_loss_loop(a, threadIdx.x, a.K), red);
+    __shared__ double red[COLMAP_WAVES][1];
+    const double acc = colmap_loss_loop(a, threadIdx.x, a.K);
+    double tot;
+    block_totals<1, COLMAP_WAVES>(&acc, red, &tot);
     if (threadIdx.x == 0) a.out[0] = (float)colmap_total(tot, a.B);
 }
 // K > COLMAP_CHUNK, one workgroup per chunk of rows: its total at ws[chunk]
 __global__ void __launch_bounds__(COLMAP_BLOCK) colmap_loss_partial_kernel(ColmapLossArgs a) {
-    __shared__ double red[COLMAP_WAVES];
+    __shared__ double red[COLMAP_WAVES][1];
     const int first = (int)blockIdx.x * COLMAP_CHUNK;
-    const double tot = colmap_block_total(colmap_loss_loop(a, first + (int)threadIdx.x, min(a.K, first + COLMAP_CHUNK)), red);
+    const double acc = colmap_loss_loop(a, first + (int)threadIdx.x, min(a.K, first + COLMAP_CHUNK));
+    double tot;
+    block_totals<1, COLMAP_WAVES>(&acc, red, &tot);
     if (threadIdx.x == 0) a.ws[blockIdx.x] = tot;
 }
 // the partial totals added in chunk order
 __global__ void colmap_loss_finish_kernel(ColmapLossArgs a, int chunks) {
-    double tot = 0.0;
-    for (int c = 0; c < chunks; ++c) tot += a.ws[c];
+    double tot;
+    sum_parts<1>(a.ws, chunks, &tot);
     a.out[0] = (float)colmap_total(tot, a.B);
 }
 

@@ -3,21 +3,22 @@
 // :277-283) and loss (:293-312) -- and the gathers that are the backward of the first two.  The arithmetic of a point is dcons.h's; this
 // file owns the loops, the ordered compaction and the reductions.
 //
-// Compaction keeps source order and uses no atomics: inside a wave a kept point's rank is the popcount of the ballot below its lane, the
-// waves' totals go through LDS in wave order, and a running base is carried across tiles of DCONS_BLOCK consecutive points, so a tile's
-// rows are contiguous.  Up to DCONS_CHUNK points one workgroup does all of it in one launch; above, a counts launch over chunks of
-// DCONS_CHUNK points and a write launch in which each workgroup adds the counts of the chunks before it in chunk order.  The sums of the
-// loss follow reproj.hip: a thread adds its points in index order, a wave its lanes by an xor butterfly, the waves in wave order, the
-// chunks in chunk order.  No host synchronisation, no readback: `count` stays in device memory.
+// Compaction keeps source order and uses no atomics (ordered.h: ordered_compact_range, in tiles of DCONS_BLOCK consecutive points).  Up
+// to DCONS_CHUNK points one workgroup does all of it in one launch; above, a counts launch over chunks of DCONS_CHUNK points and a write
+// launch in which each workgroup adds the counts of the chunks before it in chunk order.  The sums of the loss are fixed-order
+// (ordered.h: block_totals, sum_parts): a thread adds its points in index order, then the wave, the waves and the chunks in their order.
+// No host synchronisation, no readback: `count` stays in device memory.
 #include <hip/hip_runtime.h>
 
 #include "dcons.h"
+#include "ordered.h"
 
 namespace sparf {
 
 static constexpr int DCONS_WAVES = DCONS_BLOCK / 64;
 
-// ---- what is compacted: `keep(k)` evaluates point k and holds its row, `store(k, j)` writes it as output row j
+// ---- what is compacted (the items of ordered_compact_range): `keep(k)` evaluates point k and holds its row, `place(k, j)` writes it
+// as output row j with src, `mark(k, j)` leaves dst
 struct DconsProjectItem {
     typedef DconsProjectArgs Args;
     typedef DconsSetup Shared;
@@ -40,11 +41,14 @@ struct DconsProjectItem {
         z = (float)p.X[2];
         return dcons_inside(u, v, z, a.u_max, a.v_max, s.depth_min);
     }
-    __device__ void store(int k, int j) const {
+    __device__ void flags(int k, bool in, bool (&f)[1]) { f[0] = in && keep(k); }
+    __device__ void place(int k, int j) const {
         a.uv[2 * (size_t)j] = u;
         a.uv[2 * (size_t)j + 1] = v;
         a.z[j] = z;
+        a.src[j] = k;
     }
+    __device__ void mark(int k, int j) const { a.dst[k] = j; }
 };
 
 struct DconsSelectItem {
@@ -58,54 +62,33 @@ struct DconsSelectItem {
         vis = a.vis[k];
         return vis >= a.thresh;                          // tensor.ge(0.2): an fp32 compare
     }
-    __device__ void store(int k, int j) const {
+    __device__ void flags(int k, bool in, bool (&f)[1]) { f[0] = in && keep(k); }
+    __device__ void place(int k, int j) const {
         a.uv_out[2 * (size_t)j] = a.uv[2 * (size_t)k];
         a.uv_out[2 * (size_t)j + 1] = a.uv[2 * (size_t)k + 1];
         a.z_out[j] = a.z[k];
         a.vis_out[j] = vis;
+        a.src[j] = k;
     }
+    __device__ void mark(int k, int j) const { a.dst[k] = j; }
 };
 
-// the points [first, end) in tiles of DCONS_BLOCK, by one workgroup: -> base + the number kept (in every thread).  `write`: leave the
-// rows, dst and src; otherwise count only.
+// the points [first, end) by one workgroup: -> base + the number kept (in every thread).  `write`: leave the rows, dst and src;
+// otherwise count only.
 template <class Item>
 static __device__ int dcons_compact_range(const typename Item::Args& a, const typename Item::Shared& sh, int first, int end, int base, bool write,
-                                          int* wave_tot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+                                          int (*wave_tot)[1]) {
     Item item(a, sh);
-    for (int t0 = first; t0 < end; t0 += DCONS_BLOCK) {
-        const int k = t0 + (int)threadIdx.x;
-        const bool flag = k < end && item.keep(k);
-        const unsigned long long ballot = __ballot(flag);
-        if (lane == 0) wave_tot[wave] = __popcll(ballot);
-        __syncthreads();
-        int off = base, total = 0;
-#pragma unroll
-        for (int w = 0; w < DCONS_WAVES; ++w) {
-            const int c = wave_tot[w];
-            if (w < wave) off += c;
-            total += c;
-        }
-        if (write && k < end) {
-            int j = -1;
-            if (flag) {
-                j = off + __popcll(ballot & ((1ull << lane) - 1ull));
-                item.store(k, j);
-                a.src[j] = k;
-            }
-            a.dst[k] = j;
-        }
-        base += total;
-        __syncthreads();                                 // wave_tot is written again by the next tile
-    }
-    return base;
+    int run[1] = {base};
+    ordered_compact_range<DCONS_BLOCK>(item, first, end, write, run, wave_tot);
+    return run[0];
 }
 
 // n <= DCONS_CHUNK (or no workspace): one workgroup, every tile in turn
 template <class Item>
 __global__ void __launch_bounds__(DCONS_BLOCK) dcons_compact_single_kernel(typename Item::Args a) {
     __shared__ typename Item::Shared sh;
-    __shared__ int wave_tot[DCONS_WAVES];
+    __shared__ int wave_tot[DCONS_WAVES][1];
     if (threadIdx.x == 0) Item::setup(a, sh);
     __syncthreads();
     const int total = dcons_compact_range<Item>(a, sh, 0, a.n, 0, true, wave_tot);
@@ -116,7 +99,7 @@ __global__ void __launch_bounds__(DCONS_BLOCK) dcons_compact_single_kernel(typen
 template <class Item>
 __global__ void __launch_bounds__(DCONS_BLOCK) dcons_compact_counts_kernel(typename Item::Args a) {
     __shared__ typename Item::Shared sh;
-    __shared__ int wave_tot[DCONS_WAVES];
+    __shared__ int wave_tot[DCONS_WAVES][1];
     if (threadIdx.x == 0) Item::setup(a, sh);
     __syncthreads();
     const int first = (int)blockIdx.x * DCONS_CHUNK;
@@ -129,7 +112,7 @@ __global__ void __launch_bounds__(DCONS_BLOCK) dcons_compact_counts_kernel(typen
 template <class Item>
 __global__ void __launch_bounds__(DCONS_BLOCK) dcons_compact_write_kernel(typename Item::Args a) {
     __shared__ typename Item::Shared sh;
-    __shared__ int wave_tot[DCONS_WAVES];
+    __shared__ int wave_tot[DCONS_WAVES][1];
     if (threadIdx.x == 0) Item::setup(a, sh);
     __syncthreads();
     int base = 0;
@@ -197,26 +180,6 @@ __global__ void __launch_bounds__(DCONS_BLOCK) dcons_select_bwd_kernel(const int
 }
 
 // ---- the loss: totals and seeds from one pass (the normaliser 1 / (n + 1e-6) is known before the launch)
-// the totals of a workgroup, in every thread: wave butterfly, then the waves in order (the scheme of reproj_block_totals)
-static __device__ void dcons_block_totals(const double acc[DCONS_NACC], double (*red)[DCONS_NACC], double tot[DCONS_NACC]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < DCONS_NACC; ++j) {
-        double v = acc[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-        if (lane == 0) red[wave][j] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < DCONS_NACC; ++j) {
-        double v = red[0][j];
-#pragma unroll
-        for (int w = 1; w < DCONS_WAVES; ++w) v += red[w][j];
-        tot[j] = v;
-    }
-}
-
 // the points first, first + DCONS_BLOCK, ... < end into acc, their seeds stored
 static __device__ void dcons_loss_loop(const DconsLossArgs& a, int first, int end, double acc[DCONS_NACC]) {
     const double scale = dcons_scale(a.n);
@@ -240,7 +203,7 @@ __global__ void __launch_bounds__(DCONS_BLOCK) dcons_loss_single_kernel(DconsLos
     __shared__ double red[DCONS_WAVES][DCONS_NACC];
     double acc[DCONS_NACC], tot[DCONS_NACC];
     dcons_loss_loop(a, threadIdx.x, a.n, acc);
-    dcons_block_totals(acc, red, tot);
+    block_totals<DCONS_NACC, DCONS_WAVES>(acc, red, tot);
     if (threadIdx.x == 0) dcons_loss_outputs(a, tot);
 }
 // n > DCONS_CHUNK, one workgroup per chunk: its totals at ws[b]
@@ -249,7 +212,7 @@ __global__ void __launch_bounds__(DCONS_BLOCK) dcons_loss_partial_kernel(DconsLo
     double acc[DCONS_NACC], tot[DCONS_NACC];
     const int first = (int)blockIdx.x * DCONS_CHUNK;
     dcons_loss_loop(a, first + (int)threadIdx.x, min(a.n, first + DCONS_CHUNK), acc);
-    dcons_block_totals(acc, red, tot);
+    block_totals<DCONS_NACC, DCONS_WAVES>(acc, red, tot);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int j = 0; j < DCONS_NACC; ++j) a.ws[(size_t)blockIdx.x * DCONS_NACC + j] = tot[j];
@@ -257,10 +220,8 @@ __global__ void __launch_bounds__(DCONS_BLOCK) dcons_loss_partial_kernel(DconsLo
 }
 // the partial totals added in workgroup order
 __global__ void dcons_loss_finish_kernel(DconsLossArgs a, int chunks) {
-    double tot[DCONS_NACC] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = 0; b < chunks; ++b)
-#pragma unroll
-        for (int j = 0; j < DCONS_NACC; ++j) tot[j] += a.ws[(size_t)b * DCONS_NACC + j];
+    double tot[DCONS_NACC];
+    sum_parts<DCONS_NACC>(a.ws, chunks, tot);
     dcons_loss_outputs(a, tot);
 }
 

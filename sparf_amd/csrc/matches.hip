@@ -3,44 +3,35 @@
 // and the row order of the five boolean selections) and gather (the permutation's five gathers, with the rounding of :326-328 done for the
 // selected rows only).  The logic of a pixel is matches.h's; this file owns the ordered compaction, the gather and the entry points.
 //
-// Compaction: the scheme of dcons.hip, written afresh for a byte mask (dcons.hip is untouched).  It keeps row-major order and uses no
-// atomics: inside a wave a kept pixel's rank is the popcount of the wave64 ballot below its lane, the four waves' totals go through LDS
-// in wave order, and a running base is carried across tiles of MATCH_BLOCK consecutive pixels.  Up to MATCH_CHUNK pixels one workgroup
-// does all of it in one launch; above, a counts launch over chunks of MATCH_CHUNK pixels and a write launch in which each workgroup adds
-// the counts of the chunks before it in chunk order.  No workgroup waits for another inside a launch.  `count` stays in device memory.
+// Compaction keeps row-major order and uses no atomics (ordered.h: ordered_compact_range, in tiles of MATCH_BLOCK consecutive pixels).
+// Up to MATCH_CHUNK pixels one workgroup does all of it in one launch; above, a counts launch over chunks of MATCH_CHUNK pixels and a
+// write launch in which each workgroup adds the counts of the chunks before it in chunk order.  `count` stays in device memory.
 // Gather: one thread per selected row; the maps are read in place (channel-first correspondences, any channel stride).  Every address
 // comes from the index list -- clamped against the device count and the image size -- and none from a value read out of a map.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sparf_hip.h"
 #include "matches.h"
+#include "ordered.h"
 
 namespace sparf {
 
 static constexpr int MATCH_WAVES = MATCH_BLOCK / 64;
 
-// the pixels [first, end) in tiles of MATCH_BLOCK, by one workgroup: -> base + the number kept (in every thread).  `write`: leave the
-// indices; otherwise count only.
-static __device__ int match_compact_range(const MatchCompactArgs& a, int first, int end, int base, bool write, int* wave_tot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int t0 = first; t0 < end; t0 += MATCH_BLOCK) {
-        const int p = t0 + (int)threadIdx.x;
-        const bool flag = p < end && match_keep(a.mask, p, a.W, a.win);
-        const unsigned long long ballot = __ballot(flag);
-        if (lane == 0) wave_tot[wave] = __popcll(ballot);
-        __syncthreads();
-        int off = base, total = 0;
-#pragma unroll
-        for (int w = 0; w < MATCH_WAVES; ++w) {
-            const int c = wave_tot[w];
-            if (w < wave) off += c;
-            total += c;
-        }
-        if (write && flag) a.index[off + __popcll(ballot & ((1ull << lane) - 1ull))] = p;       // (rank < n: at most every pixel is kept)
-        base += total;
-        __syncthreads();                                 // wave_tot is written again by the next tile
-    }
-    return base;
+// what is compacted (the item of ordered_compact_range): the pixels of the mask inside the window, their flat indices as the rows
+struct MatchItem {
+    const MatchCompactArgs& a;
+    __device__ void flags(int p, bool in, bool (&f)[1]) const { f[0] = in && match_keep(a.mask, p, a.W, a.win); }
+    __device__ void place(int p, int j) const { a.index[j] = p; }
+    __device__ void mark(int, int) const {}
+};
+
+// the pixels [first, end) by one workgroup: -> base + the number kept (in every thread).  `write`: leave the indices; otherwise count only.
+static __device__ int match_compact_range(const MatchCompactArgs& a, int first, int end, int base, bool write, int (*wave_tot)[1]) {
+    MatchItem item{a};
+    int run[1] = {base};
+    ordered_compact_range<MATCH_BLOCK>(item, first, end, write, run, wave_tot);
+    return run[0];
 }
 
 static __device__ void match_totals(const MatchCompactArgs& a, int total) {
@@ -50,14 +41,14 @@ static __device__ void match_totals(const MatchCompactArgs& a, int total) {
 
 // n <= MATCH_CHUNK (or no workspace): one workgroup, every tile in turn
 __global__ void __launch_bounds__(MATCH_BLOCK) match_compact_single_kernel(MatchCompactArgs a) {
-    __shared__ int wave_tot[MATCH_WAVES];
+    __shared__ int wave_tot[MATCH_WAVES][1];
     const int total = match_compact_range(a, 0, a.n, 0, true, wave_tot);
     if (threadIdx.x == 0) match_totals(a, total);
 }
 
 // n > MATCH_CHUNK, one workgroup per chunk: the number kept of chunk b at ws[b]
 __global__ void __launch_bounds__(MATCH_BLOCK) match_compact_counts_kernel(MatchCompactArgs a) {
-    __shared__ int wave_tot[MATCH_WAVES];
+    __shared__ int wave_tot[MATCH_WAVES][1];
     const int first = (int)blockIdx.x * MATCH_CHUNK;
     const int total = match_compact_range(a, first, min(a.n, first + MATCH_CHUNK), 0, false, wave_tot);
     if (threadIdx.x == 0) a.ws[blockIdx.x] = total;
@@ -65,7 +56,7 @@ __global__ void __launch_bounds__(MATCH_BLOCK) match_compact_counts_kernel(Match
 
 // same grid: every workgroup adds the counts of the chunks before it in chunk order and writes its chunk; the last one leaves the count
 __global__ void __launch_bounds__(MATCH_BLOCK) match_compact_write_kernel(MatchCompactArgs a) {
-    __shared__ int wave_tot[MATCH_WAVES];
+    __shared__ int wave_tot[MATCH_WAVES][1];
     int base = 0;
     for (int b = 0; b < (int)blockIdx.x; ++b) base += a.ws[b];
     const int first = (int)blockIdx.x * MATCH_CHUNK;

@@ -7,37 +7,18 @@
 // [0, HW) is the caller's error (torch raises on it); it is clamped here so that the launch stays inside the image.
 // Depth patches: a row sums over the P^2 partners of its own patch (read from global memory, wherever the patch lies relative to a
 // chunk of rows), so every row's patch sum and seed are its own and no patch is split between workgroups.
-// Sums follow reproj.hip and dcons.hip: a thread adds its rows in index order, a wave its lanes by an xor butterfly, the waves in wave
-// order, the chunks in chunk order.  Up to PHOTO_CHUNK rows (or without a workspace) one workgroup does all of it in one launch; above,
+// Sums are fixed-order (ordered.h: block_totals, sum_parts): a thread adds its rows in index order, then the wave, the waves and the
+// chunks in their order.  Up to PHOTO_CHUNK rows (or without a workspace) one workgroup does all of it in one launch; above,
 // a launch of one workgroup per chunk that leaves partial totals and a second one that adds them.  No host synchronisation, no readback.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sparf_hip.h"
+#include "ordered.h"
 #include "photo.h"
 
 namespace sparf {
 
 static constexpr int PHOTO_WAVES = PHOTO_BLOCK / 64;
-
-// the totals of a workgroup, in every thread: wave butterfly, then the waves in order
-static __device__ void photo_block_totals(const double acc[PHOTO_NACC], double (*red)[PHOTO_NACC], double tot[PHOTO_NACC]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < PHOTO_NACC; ++j) {
-        double v = acc[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-        if (lane == 0) red[wave][j] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PHOTO_NACC; ++j) {
-        double v = red[0][j];
-#pragma unroll
-        for (int w = 1; w < PHOTO_WAVES; ++w) v += red[w][j];
-        tot[j] = v;
-    }
-}
 
 struct PhotoDepths {             // the depths of one patch, by position
     const float* p;
@@ -108,7 +89,7 @@ __global__ void __launch_bounds__(PHOTO_BLOCK) photo_regu_single_kernel(PhotoArg
     __shared__ double red[PHOTO_WAVES][PHOTO_NACC];
     double acc[PHOTO_NACC], tot[PHOTO_NACC];
     photo_loop(a, threadIdx.x, a.rows, acc);
-    photo_block_totals(acc, red, tot);
+    block_totals<PHOTO_NACC, PHOTO_WAVES>(acc, red, tot);
     if (threadIdx.x == 0) photo_outputs(a, tot);
 }
 // rows > PHOTO_CHUNK, one workgroup per chunk: its totals at ws[b]
@@ -117,7 +98,7 @@ __global__ void __launch_bounds__(PHOTO_BLOCK) photo_regu_partial_kernel(PhotoAr
     double acc[PHOTO_NACC], tot[PHOTO_NACC];
     const int first = (int)blockIdx.x * PHOTO_CHUNK;
     photo_loop(a, first + (int)threadIdx.x, min(a.rows, first + PHOTO_CHUNK), acc);
-    photo_block_totals(acc, red, tot);
+    block_totals<PHOTO_NACC, PHOTO_WAVES>(acc, red, tot);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int j = 0; j < PHOTO_NACC; ++j) a.ws[(size_t)blockIdx.x * PHOTO_NACC + j] = tot[j];
@@ -126,11 +107,7 @@ __global__ void __launch_bounds__(PHOTO_BLOCK) photo_regu_partial_kernel(PhotoAr
 // the partial totals added in chunk order
 __global__ void photo_regu_finish_kernel(PhotoArgs a, int chunks) {
     double tot[PHOTO_NACC];
-#pragma unroll
-    for (int j = 0; j < PHOTO_NACC; ++j) tot[j] = 0.0;
-    for (int b = 0; b < chunks; ++b)
-#pragma unroll
-        for (int j = 0; j < PHOTO_NACC; ++j) tot[j] += a.ws[(size_t)b * PHOTO_NACC + j];
+    sum_parts<PHOTO_NACC>(a.ws, chunks, tot);
     photo_outputs(a, tot);
 }
 

@@ -2,38 +2,23 @@
 // corres_loss.py:183-219 with both pose compositions -- with the loss, the stats, the valid mask and every gradient seed from one call.
 // The arithmetic of a match, of a term's totals and of the compositions is reproj.h's; this file owns the loops and the reductions.
 //
-// Reductions are fixed-order and use no atomics: a thread adds its matches in index order, a wave adds its lanes by an xor butterfly
-// (every lane ends with the same bits), the waves' sums are added in wave order from LDS, and above REPROJ_SINGLE_MAX matches the
-// workgroups' partial totals are added in workgroup order.  The normaliser 1 / (#valid + 1e-6) is known only after the count, so a
+// Reductions are fixed-order and use no atomics (ordered.h: block_totals, sum_parts); above REPROJ_SINGLE_MAX matches the workgroups'
+// partial totals are added in workgroup order.  The normaliser 1 / (#valid + 1e-6) is known only after the count, so a
 // term is evaluated twice: once for its totals, once -- with the scale in hand -- for the seeds, each of which is then a double
 // product rounded once.  Up to REPROJ_SINGLE_MAX matches one workgroup does all of it in one launch; above, a totals launch and a
 // seeds launch, REPROJ_PARTS workgroups per term.  No host synchronisation, no readback.
 #include <hip/hip_runtime.h>
 
+#include "ordered.h"
 #include "reproj.h"
 
 namespace sparf {
 
 static constexpr int REPROJ_WAVES = REPROJ_BLOCK / 64;
 
-// the totals of a workgroup, in every thread: wave butterfly, then the waves in order
+// the totals of a workgroup, in every thread
 static REPROJ_DEV void reproj_block_totals(const double acc[REPROJ_NACC], double (*red)[REPROJ_NACC], double tot[REPROJ_NACC]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < REPROJ_NACC; ++j) {
-        double v = acc[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-        if (lane == 0) red[wave][j] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < REPROJ_NACC; ++j) {
-        double v = red[0][j];
-#pragma unroll
-        for (int w = 1; w < REPROJ_WAVES; ++w) v += red[w][j];
-        tot[j] = v;
-    }
+    block_totals<REPROJ_NACC, REPROJ_WAVES>(acc, red, tot);
     __syncthreads();                         // red is written again by the next term
 }
 
@@ -99,15 +84,9 @@ __global__ void __launch_bounds__(REPROJ_BLOCK) reproj_partial_kernel(ReprojArgs
     }
 }
 
-// the partial totals of term t added in workgroup order
+// the partial totals of term t, ws[t][REPROJ_PARTS], added in workgroup order
 static REPROJ_DEV void reproj_sum_parts(const double* ws, int t, int parts, double tot[REPROJ_NACC]) {
-#pragma unroll
-    for (int j = 0; j < REPROJ_NACC; ++j) tot[j] = 0.0;
-    for (int b = 0; b < parts; ++b) {
-        const double* p = ws + ((size_t)t * REPROJ_PARTS + b) * REPROJ_NACC;
-#pragma unroll
-        for (int j = 0; j < REPROJ_NACC; ++j) tot[j] += p[j];
-    }
+    sum_parts<REPROJ_NACC>(ws + (size_t)t * REPROJ_PARTS * REPROJ_NACC, parts, tot);
 }
 
 // same grid: every workgroup adds the partials of its term (the same sum in the same order everywhere) and writes its share of the

@@ -87,6 +87,21 @@ def test_emulated_linear_is_the_plain_one_without_rounding():
         assert torch.allclose(a, r, rtol=1e-5, atol=1e-6)
 
 
+def test_loss_units_take_ordered_compaction_and_block_sums_from_ordered_h():
+    """The loss kernels' two promises -- a selection in torch.where's order bit for bit, sums with the same bits from call to call --
+    rest on the wave ballot ranks and the fixed-order block sums of csrc/ordered.h.  The five units call that one copy: each includes
+    the header and holds no ballot and no shuffle butterfly of its own, comments included (a sixth loss unit belongs in the list)."""
+    from sparf_amd import build as B
+    assert "ordered.h" in B.HEADERS, "source_hash() does not cover ordered.h"
+    header = open(os.path.join(B.CSRC, "ordered.h")).read()
+    assert "__ballot" in header and "__shfl_xor" in header
+    for unit in ("reproj.hip", "dcons.hip", "photo.hip", "matches.hip", "colmap.hip"):
+        text = open(os.path.join(B.CSRC, unit)).read()
+        assert '#include "ordered.h"' in text, f"{unit} does not include ordered.h"
+        for word in ("__ballot", "__shfl_xor"):
+            assert word not in text, f"{unit} has a {word} of its own: the routine lives in ordered.h"
+
+
 def test_shipped_kernels_have_no_experiment_or_probe_flag_on():
     """The kernel sources hold the shipped configuration and the instruments still in use.  The switches of settled
     experiments are retired: their names appear in no code file (the documents keep the record).  The switches that stay have the
