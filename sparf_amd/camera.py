@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .patcher import Patcher
 
 
 def to_hom(X):
@@ -225,28 +226,20 @@ class Pose:
 lie = Lie()
 pose = Pose()
 
-_patched = []
+_installer = Patcher("sparf_amd.camera.install", "uninstall")
 
 
 def install(camera_module, two_columns_module=None):
     """Opt-in: put the functions above under a trainer's own names -- `camera_module.lie.se3_to_SE3`,
     `camera_module.pose.compose_pair_b_at_a` (its `compose` goes through it) and, if given, `two_columns_module.r6d2mat` -- until
     `uninstall()`.  Nothing in this package calls it."""
-    if _patched:
-        raise RuntimeError("sparf_amd.camera.install: already installed; call uninstall() first")
+    _installer.guard()
     targets = [(camera_module.lie, "se3_to_SE3", lie.se3_to_SE3), (camera_module.pose, "compose_pair_b_at_a", pose.compose_pair_b_at_a)]
     if two_columns_module is not None:
         targets.append((two_columns_module, "r6d2mat", r6d2mat))
     for obj, name, fn in targets:
-        own = name in vars(obj)              # (a method lives on the class: the instance then goes back to having none of its own)
-        _patched.append((obj, name, own, vars(obj).get(name)))
-        setattr(obj, name, fn)
+        _installer.put(obj, name, fn)        # (a method lives on the class: the instance then goes back to having none of its own)
 
 
 def uninstall():
-    while _patched:
-        obj, name, own, old = _patched.pop()
-        if own:
-            setattr(obj, name, old)
-        else:
-            delattr(obj, name)
+    _installer.restore()

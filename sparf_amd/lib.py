@@ -219,6 +219,22 @@ def on(device):
     return torch.cuda.device(device)
 
 
+def call(name, device, *args):
+    """One entry point of the library that takes the stream last, on `device` and its current stream, its return code checked under
+    `name`.  It adds nothing of its own: no synchronisation, no allocation, no readback.  (load, on, stream_ptr and check are looked
+    up when it runs: the tests' stand-ins replace them on this module.)"""
+    lib = load()
+    with on(device):
+        check(getattr(lib, name)(*args, stream_ptr(device)), name)
+
+
+def workspace(nbytes, device, dtype):
+    """the scratch area of a call from what its *_workspace_bytes query answered, in elements of `dtype` (float64 sums, int32 counts);
+    None for no bytes: the calls below their one-workgroup limit take a null pointer"""
+    nbytes = int(nbytes)
+    return torch.empty(nbytes // dtype.itemsize, device=device, dtype=dtype) if nbytes else None
+
+
 def tables_host(prec):
     """Static gather tables (numpy int32), built by the library's host code."""
     if prec not in _tables_host:

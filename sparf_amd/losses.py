@@ -36,6 +36,7 @@ import contextlib
 import torch
 
 from . import ops
+from .patcher import Patcher
 
 LOSS_TYPES = tuple(ops.REPROJ_LOSS_TYPES)
 STAT_KEYS = ("perc_val_pix_rep", "perc_val_depth_rep", "depth_in_corr_loss")
@@ -221,26 +222,18 @@ def compute_render_and_repro_loss_w_repro_thres(self, opt, pixels_in_self_int, d
 
 
 METHOD = "compute_render_and_repro_loss_w_repro_thres"
-_patched = []
+_corres = Patcher("sparf_amd.losses.install", "uninstall")
 
 
 def install(corres_loss_module):
     """Opt-in: put the method above on `corres_loss_module.CorrespondencesPairRenderDepthAndGet3DPtsAndReproject` until `uninstall()`.
     Nothing in this package calls it."""
-    if _patched:
-        raise RuntimeError("sparf_amd.losses.install: already installed; call uninstall() first")
-    cls = corres_loss_module.CorrespondencesPairRenderDepthAndGet3DPtsAndReproject
-    _patched.append((cls, METHOD, METHOD in vars(cls), vars(cls).get(METHOD)))
-    setattr(cls, METHOD, compute_render_and_repro_loss_w_repro_thres)
+    _corres.guard()
+    _corres.put(corres_loss_module.CorrespondencesPairRenderDepthAndGet3DPtsAndReproject, METHOD, compute_render_and_repro_loss_w_repro_thres)
 
 
 def uninstall():
-    while _patched:
-        obj, name, own, old = _patched.pop()
-        if own:
-            setattr(obj, name, old)
-        else:
-            delattr(obj, name)
+    _corres.restore()
 
 
 # ================================================================================================ the depth-consistency loss
@@ -365,26 +358,18 @@ def compute_loss_at_sampled_pose(self, data_dict, pose_w2c_at_unseen, intr_at_un
 
 
 DCONS_METHOD = "compute_loss_at_sampled_pose"
-_patched_dcons = []
+_dcons = Patcher("sparf_amd.losses.install_depth_consistency", "uninstall_depth_consistency")
 
 
 def install_depth_consistency(depth_cons_loss_module):
     """Opt-in, and independent of install(): put the method above on `depth_cons_loss_module.DepthConsistencyLoss` until
     `uninstall_depth_consistency()`.  Nothing in this package calls it."""
-    if _patched_dcons:
-        raise RuntimeError("sparf_amd.losses.install_depth_consistency: already installed; call uninstall_depth_consistency() first")
-    cls = depth_cons_loss_module.DepthConsistencyLoss
-    _patched_dcons.append((cls, DCONS_METHOD, DCONS_METHOD in vars(cls), vars(cls).get(DCONS_METHOD)))
-    setattr(cls, DCONS_METHOD, compute_loss_at_sampled_pose)
+    _dcons.guard()
+    _dcons.put(depth_cons_loss_module.DepthConsistencyLoss, DCONS_METHOD, compute_loss_at_sampled_pose)
 
 
 def uninstall_depth_consistency():
-    while _patched_dcons:
-        obj, name, own, old = _patched_dcons.pop()
-        if own:
-            setattr(obj, name, old)
-        else:
-            delattr(obj, name)
+    _dcons.restore()
 
 
 # ================================================================================================ the photometric, mask and depth-patch loss
@@ -531,7 +516,7 @@ def mse_on_rays(data_dict, output_dict):
     return mse, (mse_fine if rgb_fine is not None else None)
 
 
-_original_photo = []             # the class's own compute_loss, saved by install_photometric: the distortion hand-over calls it
+_photo = Patcher("sparf_amd.losses.install_photometric", "uninstall_photometric")     # keeps the class's own compute_loss: the distortion hand-over calls it
 
 
 def compute_loss(self, opt, data_dict, output_dict, iteration, mode=None, plot=False, **kwargs):
@@ -541,10 +526,11 @@ def compute_loss(self, opt, data_dict, output_dict, iteration, mode=None, plot=F
     needs gradients to per-sample weights that the call does not give."""
     from .edict import EasyDict as edict
     if opt.loss_weight.distortion is not None:
-        if not _original_photo or _original_photo[-1] is None:
+        original = _photo.original(PHOTO_METHOD)
+        if original is None:
             raise RuntimeError("sparf_amd.losses.compute_loss: loss_weight.distortion is set and there is no original method to hand it to "
                                "(install_photometric() saves it)")
-        return _original_photo[-1](self, opt, data_dict, output_dict, iteration, mode=mode, plot=plot, **kwargs)
+        return original(self, opt, data_dict, output_dict, iteration, mode=mode, plot=plot, **kwargs)
     loss_dict = edict(render=torch.tensor(0., requires_grad=True).to(self.device))
     if iteration < self.opt.start_iter.photometric:
         return loss_dict, {}, {}
@@ -566,32 +552,20 @@ def compute_loss(self, opt, data_dict, output_dict, iteration, mode=None, plot=F
     return loss_dict, {}, {}
 
 
-_patched_photo = []
-
-
 def install_photometric(base_losses_module, trainer_module=None):
     """Opt-in, and independent of install() and install_depth_consistency(): put compute_loss above on
     `base_losses_module.BasePhotoandReguLoss` and, with `trainer_module` (a module that imported the name, as nerf_trainer does), mse_on_rays
     under its `compute_mse_on_rays`, until `uninstall_photometric()`.  Nothing in this package calls it."""
-    if _patched_photo:
-        raise RuntimeError("sparf_amd.losses.install_photometric: already installed; call uninstall_photometric() first")
+    _photo.guard()
     cls = base_losses_module.BasePhotoandReguLoss
-    _original_photo.append(getattr(cls, PHOTO_METHOD, None))
-    _patched_photo.append((cls, PHOTO_METHOD, PHOTO_METHOD in vars(cls), vars(cls).get(PHOTO_METHOD)))
-    setattr(cls, PHOTO_METHOD, compute_loss)
+    _photo.save(PHOTO_METHOD, getattr(cls, PHOTO_METHOD, None))
+    _photo.put(cls, PHOTO_METHOD, compute_loss)
     if trainer_module is not None:
-        _patched_photo.append((trainer_module, MSE_NAME, MSE_NAME in vars(trainer_module), vars(trainer_module).get(MSE_NAME)))
-        setattr(trainer_module, MSE_NAME, mse_on_rays)
+        _photo.put(trainer_module, MSE_NAME, mse_on_rays)
 
 
 def uninstall_photometric():
-    while _patched_photo:
-        obj, name, own, old = _patched_photo.pop()
-        if own:
-            setattr(obj, name, old)
-        else:
-            delattr(obj, name)
-    del _original_photo[:]
+    _photo.restore()
 
 
 # ================================================================================================ the correspondence sampler
@@ -705,7 +679,7 @@ def select_matches(mask, corres_map, conf_map, max_matches, *, window=None, perm
     return (*rows, count, perc)
 
 
-_original_sampler = {}           # the classes' own methods, saved by install_sampler: the debug configurations are handed to them
+_sampler = Patcher("sparf_amd.losses.install_sampler", "uninstall_sampler")     # keeps the classes' own methods: the debug configurations are handed to them
 
 
 def _opt(opt, key, default=None):
@@ -713,10 +687,11 @@ def _opt(opt, key, default=None):
 
 
 def _handed_over(self, name):
-    if _original_sampler.get(name) is None:
+    original = _sampler.original(name)
+    if original is None:
         raise RuntimeError(f"sparf_amd.losses.{name}: a debug configuration (use_gt_correspondences / skip_verif=False) and there is no "
                            "original method to hand it to (install_sampler() saves it)")
-    return _original_sampler[name]
+    return original
 
 
 def _window_mask_torch(mask, window):
@@ -812,33 +787,22 @@ def compute_loss_on_image_pair(self, data_dict, images, poses_w2c, intrs, id_sel
     return loss_dict, stats_dict, plotting_dict
 
 
-_patched_sampler = []
-
-
 def install_sampler(corres_loss_module, base_corres_loss_module):
     """Opt-in, and independent of install(), install_depth_consistency() and install_photometric(): put compute_loss_pairwise and
     compute_loss_at_given_img_indexes above on `base_corres_loss_module.CorrespondenceBasedLoss` and compute_loss_on_image_pair on
     `corres_loss_module.CorrespondencesPairRenderDepthAndGet3DPtsAndReproject`, until `uninstall_sampler()`.  A module configured with
     use_gt_correspondences, or a call with skip_verif=False, goes to the original methods.  Nothing in this package calls it."""
-    if _patched_sampler:
-        raise RuntimeError("sparf_amd.losses.install_sampler: already installed; call uninstall_sampler() first")
+    _sampler.guard()
     base = base_corres_loss_module.CorrespondenceBasedLoss
     pair = corres_loss_module.CorrespondencesPairRenderDepthAndGet3DPtsAndReproject
     new = dict(zip(SAMPLER_METHODS, (compute_loss_pairwise, compute_loss_at_given_img_indexes, compute_loss_on_image_pair)))
     for cls, name in ((base, SAMPLER_METHODS[0]), (base, SAMPLER_METHODS[1]), (pair, SAMPLER_METHODS[2])):
-        _original_sampler[name] = getattr(cls, name, None)
-        _patched_sampler.append((cls, name, name in vars(cls), vars(cls).get(name)))
-        setattr(cls, name, new[name])
+        _sampler.save(name, getattr(cls, name, None))
+        _sampler.put(cls, name, new[name])
 
 
 def uninstall_sampler():
-    while _patched_sampler:
-        obj, name, own, old = _patched_sampler.pop()
-        if own:
-            setattr(obj, name, old)
-        else:
-            delattr(obj, name)
-    _original_sampler.clear()
+    _sampler.restore()
 
 
 # ================================================================================================ the DS-NeRF sparse depth loss
@@ -1050,23 +1014,15 @@ def compute_colmap_depth_loss(self, opt, data_dict, output_dict, iteration, mode
     return edict(colmap_depth=loss), stats_dict, {}
 
 
-_patched_colmap = []
+_colmap = Patcher("sparf_amd.losses.install_colmap_depth", "uninstall_colmap_depth")
 
 
 def install_colmap_depth(base_losses_module):
     """Opt-in, and independent of the other installs: put compute_colmap_depth_loss on `base_losses_module.SparseCOLMAPDepthLoss` under
     the name compute_loss until `uninstall_colmap_depth()`.  Nothing in this package calls it."""
-    if _patched_colmap:
-        raise RuntimeError("sparf_amd.losses.install_colmap_depth: already installed; call uninstall_colmap_depth() first")
-    cls = base_losses_module.SparseCOLMAPDepthLoss
-    _patched_colmap.append((cls, COLMAP_METHOD, COLMAP_METHOD in vars(cls), vars(cls).get(COLMAP_METHOD)))
-    setattr(cls, COLMAP_METHOD, compute_colmap_depth_loss)
+    _colmap.guard()
+    _colmap.put(base_losses_module.SparseCOLMAPDepthLoss, COLMAP_METHOD, compute_colmap_depth_loss)
 
 
 def uninstall_colmap_depth():
-    while _patched_colmap:
-        obj, name, own, old = _patched_colmap.pop()
-        if own:
-            setattr(obj, name, old)
-        else:
-            delattr(obj, name)
+    _colmap.restore()

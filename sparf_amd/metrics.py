@@ -15,6 +15,7 @@ import torch
 
 from . import ops
 from .edict import EasyDict as edict
+from .patcher import Patcher
 
 OUTS = ops.METRICS_OUTS
 WINDOW_SIZE, SIGMA = 11, 1.5
@@ -179,15 +180,16 @@ def ssim(img1, img2, window_size=WINDOW_SIZE, size_average=True):
 
 
 # ---------------------------------------------------------------------------------------------- under the reference's names
-_originals = {}                  # the reference's own functions, saved by install(): a three-channel mask is handed to them
+_installer = Patcher("sparf_amd.metrics.install", "uninstall")     # keeps the reference's own functions: a three-channel mask is handed to them
 NAMES = ("compute_metrics", "compute_metrics_masked", "ssim_loss")
 
 
 def _handed_over(name):
-    if name not in _originals:
+    original = _installer.original(name)
+    if original is None:
         raise RuntimeError(f"sparf_amd.metrics.{name}: a three-channel fg_mask goes to the reference's own function and there is none "
                            "(install() saves it)")
-    return _originals[name]
+    return original
 
 
 def _three_channel(data_dict):
@@ -240,28 +242,20 @@ def compute_metrics(data_dict, output_dict, pred_rgb_map, pred_depth, gt_rgb_map
     return results
 
 
-_patched = []
-
-
 def install(metrics_module, *importing_modules):
     """Opt-in: put compute_metrics, compute_metrics_masked and ssim (as `ssim_loss`) above under those names on `metrics_module`
     (source.training.core.metrics) and on every module given that imported one of them (base, nerf_trainer), until `uninstall()`.
     Nothing in this package calls it."""
-    if _patched:
-        raise RuntimeError("sparf_amd.metrics.install: already installed; call uninstall() first")
+    _installer.guard()
     ours = dict(compute_metrics=compute_metrics, compute_metrics_masked=compute_metrics_masked, ssim_loss=ssim)
     for name in NAMES:
         if hasattr(metrics_module, name):
-            _originals[name] = getattr(metrics_module, name)
+            _installer.save(name, getattr(metrics_module, name))
     for mod in (metrics_module, *importing_modules):
         for name in NAMES:
             if name in vars(mod):
-                _patched.append((mod, name, vars(mod)[name]))
-                setattr(mod, name, ours[name])
+                _installer.put(mod, name, ours[name])
 
 
 def uninstall():
-    while _patched:
-        mod, name, old = _patched.pop()
-        setattr(mod, name, old)
-    _originals.clear()
+    _installer.restore()

@@ -76,8 +76,7 @@ def pack_weights(params, prec, out=None):
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     tables = L.tables_device(L.base_prec(prec), dev)
-    with L.on(dev):
-        L.check(lib.sparf_pack_weights(prec, arr, L.ptr(tables), L.ptr(out), L.stream_ptr(dev)), "sparf_pack_weights")
+    L.call("sparf_pack_weights", dev, prec, arr, L.ptr(tables), L.ptr(out))
     return out
 
 
@@ -85,7 +84,6 @@ def c2f_weights(progress, barf_c2f, device):
     """The 16-float band-weight vector of one pass (frequency_nerf.py:248-253), computed on the
     device from the CURRENT value of `progress` -- never cached: the reference trainer rewrites
     progress.data every iteration (nerf_trainer.py:273-275), which no version counter sees."""
-    lib = L.load()
     L.require_gpu(device)
     if barf_c2f is None:              # no masking: the constant vector, made once per device
         dev = _resolve(device)        # a bare "cuda" must not bind the cache entry to whichever device was current first
@@ -96,8 +94,7 @@ def c2f_weights(progress, barf_c2f, device):
         return _C2F_OFF[dev]
     out = torch.empty(16, dtype=torch.float32, device=device)
     prog = _f32(progress).reshape(1).to(device)
-    with L.on(device):
-        L.check(lib.sparf_c2f_weights(L.ptr(prog), 1, float(barf_c2f[0]), float(barf_c2f[1]), L.ptr(out), L.stream_ptr(device)), "sparf_c2f_weights")
+    L.call("sparf_c2f_weights", device, L.ptr(prog), 1, float(barf_c2f[0]), float(barf_c2f[1]), L.ptr(out))
     return out
 
 
@@ -119,14 +116,12 @@ def _check_out(out, shape, device):
 def sample_coarse(nrays, nsamp, dmin, scale, inverse, device, jitter=None, u_const=0.5, dmax_ray=None, range_dev=None, out=None):
     """range_dev: optional float32 device tensor {dmin, dmax} (or {dmin}) replacing the floats.
     out: optional [nrays, nsamp] destination (a row slice of a shared ray buffer, Graph.render_batch)."""
-    lib = L.load()
     L.require_gpu(device)
     t = torch.empty(nrays, nsamp, dtype=torch.float32, device=device) if out is None else _check_out(out, (nrays, nsamp), device)
     j = _f32(jitter).reshape(nrays, nsamp) if jitter is not None else None
     dm = _f32(dmax_ray).reshape(nrays) if dmax_ray is not None else None
-    with L.on(device):
-        L.check(lib.sparf_sample_coarse(L.ptr(j), float(u_const), L.ptr(dm), L.ptr(range_dev), float(dmin), float(scale),
-                                        int(bool(inverse)), nrays, nsamp, L.ptr(t), L.stream_ptr(device)), "sparf_sample_coarse")
+    L.call("sparf_sample_coarse", device, L.ptr(j), float(u_const), L.ptr(dm), L.ptr(range_dev), float(dmin), float(scale), int(bool(inverse)),
+           nrays, nsamp, L.ptr(t))
     return t
 
 
@@ -327,7 +322,6 @@ class NerfPass(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, center, dirs, t, noise, noise_scale, white_bg, prec, packed, c2f, grad_mode, far, segs, *params):
-        lib = L.load()
         dev = center.device
         L.require_gpu(dev)
         c, d, tt = _f32(center), _f32(dirs), _f32(t)
@@ -342,8 +336,7 @@ class NerfPass(torch.autograd.Function):
         prec = pass_prec_of(prec, kind)
         ctx.set_materialize_grads(False)          # absent upstream gradients arrive as None, not as zero tensors
         a, out, save, _keep = build_pass_fwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, need_grad, segs=segs, far=far)
-        with L.on(dev):
-            L.check(lib.sparf_pass_forward(ctypes.byref(a), L.stream_ptr(dev)), "sparf_pass_forward")
+        L.call("sparf_pass_forward", dev, ctypes.byref(a))
         if need_grad:       # (far rows leave nothing of their own behind: their saves were transplanted into `save`)
             ctx.save_for_backward(c, d, tt, nz, packed, c2f, save, out["raylen"], out["sigma_raw"], out["rgb_samples"], out["weights"])
             ctx.meta = (noise_scale, int(bool(white_bg)), prec, [tuple(p.shape) for p in params], list(segs) if segs else None)
@@ -352,7 +345,6 @@ class NerfPass(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *g):
-        lib = L.load()
         c, d, tt, nz, packed, c2f, save, raylen, sigma_raw, rgb_samples, weights = ctx.saved_tensors
         noise_scale, white_bg, prec, shapes, segs = ctx.meta
         pose = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
@@ -360,8 +352,7 @@ class NerfPass(torch.autograd.Function):
         if segs:
             g = [g[9 * i:9 * i + 9] for i in range(len(segs))]
         a, gp, dc, dd, _keep = build_pass_bwd(prec, c, d, tt, nz, noise_scale, white_bg, packed, c2f, save, fwd_out, g, pose, segs=segs)
-        with L.on(c.device):
-            L.check(lib.sparf_pass_backward(ctypes.byref(a), L.stream_ptr(c.device)), "sparf_pass_backward")
+        L.call("sparf_pass_backward", c.device, ctypes.byref(a))
         return (dc if ctx.needs_input_grad[0] else None, dd if ctx.needs_input_grad[1] else None, None, None, None, None, None,
                 None, None, None, None, None, *_param_grad_views(gp, shapes, ctx.needs_input_grad[12:]))
 
@@ -405,24 +396,20 @@ def _ray_sel(pose, pixels, ray_idx):
 
 
 def _ray_gen_launch(P, K, sel, is_px, per_image, width, B, N, center, ray):
-    lib = L.load()
     Pp = L.ptr
-    with L.on(P.device):
-        L.check(lib.sparf_ray_gen_forward(Pp(P), Pp(K), Pp(sel if is_px else None), Pp(None if is_px else sel), per_image, int(width), B, N,
-                                          Pp(center), Pp(ray), L.stream_ptr(P.device)), "sparf_ray_gen_forward")
+    L.call("sparf_ray_gen_forward", P.device, Pp(P), Pp(K), Pp(sel if is_px else None), Pp(None if is_px else sel), per_image, int(width), B, N,
+           Pp(center), Pp(ray))
 
 
 def _ray_gen_pose_grad(P, K, sel, is_px, per_image, width, B, N, g_center, g_ray):
     if g_center is None and g_ray is None:
         return None
-    lib = L.load()
     gc = _f32(g_center) if g_center is not None else None
     gr = _f32(g_ray) if g_ray is not None else None
     d_pose = torch.empty(B, 3, 4, device=P.device, dtype=torch.float32)
     Pp = L.ptr
-    with L.on(P.device):
-        L.check(lib.sparf_ray_gen_backward(Pp(P), Pp(K), Pp(sel if is_px else None), Pp(None if is_px else sel), per_image, int(width), B, N,
-                                           Pp(gc), Pp(gr), Pp(d_pose), L.stream_ptr(P.device)), "sparf_ray_gen_backward")
+    L.call("sparf_ray_gen_backward", P.device, Pp(P), Pp(K), Pp(sel if is_px else None), Pp(None if is_px else sel), per_image, int(width), B, N,
+           Pp(gc), Pp(gr), Pp(d_pose))
     return d_pose
 
 
@@ -548,9 +535,7 @@ class PhotometricLoss(torch.autograd.Function):
         df = torch.empty_like(pf) if need_f else None
         P = L.ptr
         ws = torch.empty(int(lib.sparf_photometric_workspace_floats()), device=dev, dtype=torch.float32) if p.numel() > 65536 else None
-        with L.on(dev):
-            L.check(lib.sparf_photometric_loss(P(p), P(pf), P(t), p.numel(), int(kind), float(delta), P(loss), P(d), P(df), P(ws),
-                                               L.stream_ptr(dev)), "sparf_photometric_loss")
+        L.call("sparf_photometric_loss", dev, P(p), P(pf), P(t), p.numel(), int(kind), float(delta), P(loss), P(d), P(df), P(ws))
         ctx.save_for_backward(d, df)
         ctx.shapes = (rgb.shape, rgb_fine.shape if rgb_fine is not None else None)
         return loss
@@ -567,13 +552,6 @@ def photometric_loss(rgb, target, rgb_fine=None, huber=False, delta=0.5):
 
 
 # ---------------------------------------------------------------------------------------------- pose parameterisations
-def _pose_call(name, dev, *args):
-    """one entry point of the pose family on the current stream: no host synchronisation, no readback"""
-    lib = L.load()
-    with L.on(dev):
-        L.check(getattr(lib, name)(*args, L.stream_ptr(dev)), name)
-
-
 def _pose_empty(like, *shape):
     return torch.empty(*shape, device=like.device, dtype=torch.float32)
 
@@ -593,7 +571,7 @@ class Se3Pose(torch.autograd.Function):
         pose = _pose_empty(x, n, 3, 4)
         refine = _pose_empty(x, n, 3, 4) if (want_refine and b is not None) else None
         P = L.ptr
-        _pose_call("sparf_pose_se3_forward", dev, P(x), P(b), n, P(refine), P(pose))
+        L.call("sparf_pose_se3_forward", dev, P(x), P(b), n, P(refine), P(pose))
         ctx.save_for_backward(x, b)
         ctx.set_materialize_grads(False)
         return pose, refine
@@ -611,7 +589,7 @@ class Se3Pose(torch.autograd.Function):
         d_xi = _pose_empty(x, n, 6)
         d_base = _pose_empty(x, n, 3, 4) if need_base else None
         P = L.ptr
-        _pose_call("sparf_pose_se3_backward", x.device, P(x), P(b), n, P(gp), P(gr), P(d_xi), P(d_base))
+        L.call("sparf_pose_se3_backward", x.device, P(x), P(b), n, P(gp), P(gr), P(d_xi), P(d_base))
         return d_xi if need_xi else None, d_base, None
 
 
@@ -626,7 +604,7 @@ class ComposePose(torch.autograd.Function):
         n = pa.shape[0]
         out = _pose_empty(pa, n, 3, 4)
         P = L.ptr
-        _pose_call("sparf_pose_compose_forward", dev, P(pa), P(pb), n, P(out))
+        L.call("sparf_pose_compose_forward", dev, P(pa), P(pb), n, P(out))
         ctx.save_for_backward(pa, pb)
         ctx.set_materialize_grads(False)
         return out
@@ -640,7 +618,7 @@ class ComposePose(torch.autograd.Function):
         n = pa.shape[0]
         d_a, d_b = _pose_empty(pa, n, 3, 4), _pose_empty(pa, n, 3, 4)
         P = L.ptr
-        _pose_call("sparf_pose_compose_backward", pa.device, P(pa), P(pb), n, P(_f32(g)), P(d_a), P(d_b))
+        L.call("sparf_pose_compose_backward", pa.device, P(pa), P(pb), n, P(_f32(g)), P(d_a), P(d_b))
         return d_a if ctx.needs_input_grad[0] else None, d_b if ctx.needs_input_grad[1] else None
 
 
@@ -656,7 +634,7 @@ class D9Pose(torch.autograd.Function):
         n = x.shape[0]
         pose = _pose_empty(x, n, 3, 4)
         P = L.ptr
-        _pose_call("sparf_pose_d9_forward", dev, P(x), int(bool(invert)), n, P(pose))
+        L.call("sparf_pose_d9_forward", dev, P(x), int(bool(invert)), n, P(pose))
         ctx.save_for_backward(x)
         ctx.invert = int(bool(invert))
         ctx.set_materialize_grads(False)
@@ -671,7 +649,7 @@ class D9Pose(torch.autograd.Function):
         n = x.shape[0]
         d_d9 = _pose_empty(x, n, 9)
         P = L.ptr
-        _pose_call("sparf_pose_d9_backward", x.device, P(x), ctx.invert, n, P(_f32(g)), P(d_d9))
+        L.call("sparf_pose_d9_backward", x.device, P(x), ctx.invert, n, P(_f32(g)), P(d_d9))
         return d_d9, None
 
 
@@ -682,11 +660,8 @@ REPROJ_LOSS_TYPES = {"huber": 0, "l1": 1, "mse": 2, "epe": 3}          # include
 def _reproj_call(name, dev, n, head, opts, outs):
     """one entry point of the correspondence loss on the current stream: the input pointers, n and the options, the
     output pointers, the workspace (above the one-workgroup limit only) -- no host synchronisation, no readback"""
-    lib = L.load()
-    nb = int(lib.sparf_reproj_workspace_bytes(n))
-    ws = torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None
-    with L.on(dev):
-        L.check(getattr(lib, name)(*map(L.ptr, head), n, *opts, *map(L.ptr, outs), L.ptr(ws), L.stream_ptr(dev)), name)
+    ws = L.workspace(L.load().sparf_reproj_workspace_bytes(n), dev, torch.float64)
+    L.call(name, dev, *map(L.ptr, head), n, *opts, *map(L.ptr, outs), L.ptr(ws))
 
 
 def _reproj_opts(loss_type, pixel_thresh, depth_thresh):
@@ -808,13 +783,10 @@ DCONS_LOSS_TYPES = {"huber": 0, "l1": 1, "mse": 2}          # include/sparf_hip.
 def _dcons_call(name, dev, *args, ws_for=None):
     """one entry point of the depth-consistency loss on the current stream; `ws_for`: the number of points of a call
     that takes a workspace (above the one-workgroup limit only)"""
-    lib = L.load()
     tail = ()
     if ws_for is not None:
-        nb = int(lib.sparf_dcons_workspace_bytes(ws_for))
-        tail = (L.ptr(torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None),)
-    with L.on(dev):
-        L.check(getattr(lib, name)(*args, *tail, L.stream_ptr(dev)), name)
+        tail = (L.ptr(L.workspace(L.load().sparf_dcons_workspace_bytes(ws_for), dev, torch.float64)),)
+    L.call(name, dev, *args, *tail)
 
 
 def _dcons_compacted(dev, n):
@@ -1023,14 +995,10 @@ class PhotoReguLoss(torch.autograd.Function):
         head = [_flat(t, rows * (3 if i < 2 else 1), name, op, "rays") if t is not None else None for i, (t, name) in enumerate(zip(tensors, names))]
         out = torch.empty(5, device=dev, dtype=torch.float32)
         seeds = [torch.empty_like(head[i]) if (t is not None and ctx.needs_input_grad[3 + i]) else None for i, t in enumerate(tensors)]
-        lib = L.load()
-        nb = int(lib.sparf_photo_regu_workspace_bytes(rows))
-        ws = torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None
+        ws = L.workspace(L.load().sparf_photo_regu_workspace_bytes(rows), dev, torch.float64)
         p, img = L.ptr, _f32(image)
-        with L.on(dev):
-            L.check(lib.sparf_photo_regu_loss(p(img), p(fg_mask), p(ray_idx), per_image, B, HW, N, *map(p, head), PHOTO_KINDS[kind],
-                                              float(delta), patch, float(charbonnier), p(out), *map(p, seeds), p(ws), L.stream_ptr(dev)),
-                    "sparf_photo_regu_loss")
+        L.call("sparf_photo_regu_loss", dev, p(img), p(fg_mask), p(ray_idx), per_image, B, HW, N, *map(p, head), PHOTO_KINDS[kind], float(delta), patch,
+               float(charbonnier), p(out), *map(p, seeds), p(ws))
         ctx.save_for_backward(*seeds)
         ctx.shapes = [t.shape if t is not None else None for t in tensors]
         ctx.set_materialize_grads(False)
@@ -1105,12 +1073,9 @@ def match_compact(mask, window=None, want_perc=True):
     index = torch.empty(n, device=dev, dtype=torch.int32)
     count = torch.empty(1, device=dev, dtype=torch.int32)
     perc = torch.empty(1, device=dev, dtype=torch.float32) if want_perc else None
-    lib = L.load()
-    nb = int(lib.sparf_match_workspace_bytes(n))
-    ws = torch.empty(nb // 4, device=dev, dtype=torch.int32) if nb else None
+    ws = L.workspace(L.load().sparf_match_workspace_bytes(n), dev, torch.int32)
     p = L.ptr
-    with L.on(dev):
-        L.check(lib.sparf_match_compact(p(m), H, W, y0, y1, x0, x1, p(index), p(count), p(perc), p(ws), L.stream_ptr(dev)), "sparf_match_compact")
+    L.call("sparf_match_compact", dev, p(m), H, W, y0, y1, x0, x1, p(index), p(count), p(perc), p(ws))
     return index, count, perc
 
 
@@ -1132,11 +1097,8 @@ def match_gather(index, count, sel, k, H, W, corres, conf):
         sel = sel.detach().reshape(-1).contiguous()
     c, stride = _match_corres(corres, H, W)
     cf = _match_conf(conf, H, W)
-    lib = L.load()
     p = L.ptr
-    with L.on(dev):
-        L.check(lib.sparf_match_gather(p(index), p(count), p(sel), k, H, W, ctypes.c_void_p(c.data_ptr()), stride, p(cf), *map(p, outs),
-                                       L.stream_ptr(dev)), "sparf_match_gather")
+    L.call("sparf_match_gather", dev, p(index), p(count), p(sel), k, H, W, ctypes.c_void_p(c.data_ptr()), stride, p(cf), *map(p, outs))
     return outs
 
 
@@ -1168,12 +1130,9 @@ def colmap_compact(colmap_depth):
     n = H * W
     index = torch.empty(B, n, device=dev, dtype=torch.int32)
     count = torch.empty(2 * B, device=dev, dtype=torch.int32)
-    lib = L.load()
-    nb = int(lib.sparf_colmap_workspace_bytes(B, n, 0))
-    ws = torch.empty(nb // 4, device=dev, dtype=torch.int32) if nb else None
+    ws = L.workspace(L.load().sparf_colmap_workspace_bytes(B, n, 0), dev, torch.int32)
     p = L.ptr
-    with L.on(dev):
-        L.check(lib.sparf_colmap_compact(p(d), B, H, W, p(index), p(count), p(ws), L.stream_ptr(dev)), "sparf_colmap_compact")
+    L.call("sparf_colmap_compact", dev, p(d), B, H, W, p(index), p(count), p(ws))
     return index, count
 
 
@@ -1204,11 +1163,8 @@ def colmap_gather(index, count, sel, quota, K, H, W, colmap_depth, colmap_conf, 
         sel = sel.detach().reshape(-1).contiguous()
     if any(o.numel() != K for o in outs):
         raise ValueError(f"sparse depth loss: the outputs must hold {K} rows")
-    lib = L.load()
     p = L.ptr
-    with L.on(dev):
-        L.check(lib.sparf_colmap_gather(p(index[b0:b1]), p(count[b0:b1]), p(sel), b1 - b0, H, W, quota, K, p(d[b0:b1]), p(c[b0:b1]), *map(p, outs),
-                                        L.stream_ptr(dev)), "sparf_colmap_gather")
+    L.call("sparf_colmap_gather", dev, p(index[b0:b1]), p(count[b0:b1]), p(sel), b1 - b0, H, W, quota, K, p(d[b0:b1]), p(c[b0:b1]), *map(p, outs))
     return outs
 
 
@@ -1256,13 +1212,9 @@ class ColmapLoss(torch.autograd.Function):
         need_c, need_f = any(ctx.needs_input_grad[6:6 + nd]), any(ctx.needs_input_grad[6 + nd:])
         s_c = torch.empty(K, device=dev, dtype=torch.float32) if need_c else None
         s_f = torch.empty(K, device=dev, dtype=torch.float32) if need_f else None
-        lib = L.load()
-        nb = int(lib.sparf_colmap_workspace_bytes(0, 0, K))
-        ws = torch.empty(nb // 8, device=dev, dtype=torch.float64) if nb else None
+        ws = L.workspace(L.load().sparf_colmap_workspace_bytes(0, 0, K), dev, torch.float64)
         p = L.ptr
-        with L.on(dev):
-            L.check(lib.sparf_colmap_loss(p(t), p(w), p(count.detach().contiguous()), B, quota, K, p(p_c), p(p_f), p(out), p(s_c), p(s_f), p(ws),
-                                          L.stream_ptr(dev)), "sparf_colmap_loss")
+        L.call("sparf_colmap_loss", dev, p(t), p(w), p(count.detach().contiguous()), B, quota, K, p(p_c), p(p_f), p(out), p(s_c), p(s_f), p(ws))
         ctx.save_for_backward(s_c, s_f)
         ctx.shapes = [d.shape for d in depths]
         ctx.nd = nd
@@ -1343,12 +1295,10 @@ def image_metrics(pred, gt, pred_fine=None, fg_mask=None, depth=None, depth_fine
             put(name, _metrics_rows(t, B, H * W, dtypes, name))
     out = torch.empty(2, len(METRICS_OUTS), device=dev, dtype=torch.float32)
     counts = torch.empty(2, device=dev, dtype=torch.int32)
-    lib = L.load()
-    nb = int(lib.sparf_image_metrics_workspace_bytes(B, H, W))
-    ws = torch.empty(max(nb // 8, 1), device=dev, dtype=torch.float64)
+    nb = int(L.load().sparf_image_metrics_workspace_bytes(B, H, W))
+    ws = torch.empty(max(nb // 8, 1), device=dev, dtype=torch.float64)         # (always one: the struct's pointer is never null)
     a.out, a.counts, a.workspace, a.workspace_bytes = out.data_ptr(), counts.data_ptr(), ws.data_ptr(), nb
-    with L.on(dev):
-        L.check(lib.sparf_image_metrics(ctypes.byref(a), L.stream_ptr(dev)), "sparf_image_metrics")
+    L.call("sparf_image_metrics", dev, ctypes.byref(a))
     return out, counts
 
 
@@ -1361,7 +1311,6 @@ class Composite(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ray, density, rgb_samples, t, white_bg):
-        lib = L.load()
         dev = ray.device
         L.require_gpu(dev)
         d, dn, cs, tt = _f32(ray), _f32(density), _f32(rgb_samples), _f32(t)
@@ -1370,8 +1319,7 @@ class Composite(torch.autograd.Function):
         out = dict(raylen=f(R), weights=f(R, N), rgb=f(R, 3), depth=f(R), opacity=f(R), depth_var=f(R), rgb_var=f(R), all_cumulated=f(R))
         a = L.CompositeFwd(nrays=R, nsamp=N, white_bg=int(bool(white_bg)), dir=d.data_ptr(), t=tt.data_ptr(), density=dn.data_ptr(),
                            rgb_samples=cs.data_ptr(), **{k: v.data_ptr() for k, v in out.items()})
-        with L.on(dev):
-            L.check(lib.sparf_composite_forward(ctypes.byref(a), L.stream_ptr(dev)), "sparf_composite_forward")
+        L.call("sparf_composite_forward", dev, ctypes.byref(a))
         ctx.save_for_backward(d, dn, cs, tt, out["raylen"], out["weights"])
         ctx.white_bg = int(bool(white_bg))
         ctx.set_materialize_grads(False)
@@ -1379,7 +1327,6 @@ class Composite(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *g7):
-        lib = L.load()
         d, dn, cs, tt, raylen, weights = ctx.saved_tensors
         dev = d.device
         R, N = tt.shape
@@ -1393,8 +1340,7 @@ class Composite(torch.autograd.Function):
         a = L.CompositeBwd(nrays=R, nsamp=N, white_bg=ctx.white_bg, dir=P(d), t=P(tt), density=P(dn), rgb_samples=P(cs), raylen=P(raylen),
                            weights=P(weights), g_rgb=P(gs[0]), g_depth=P(gs[1]), g_opacity=P(gs[2]), g_weights=P(gs[3]), g_depth_var=P(gs[4]),
                            g_rgb_var=P(gs[5]), g_all_cumulated=P(gs[6]), d_density=P(d_dens), d_rgb_samples=P(d_rgbs), d_dir=P(d_dir), d_len_ws=P(d_len))
-        with L.on(dev):
-            L.check(lib.sparf_composite_backward(ctypes.byref(a), L.stream_ptr(dev)), "sparf_composite_backward")
+        L.call("sparf_composite_backward", dev, ctypes.byref(a))
         return d_dir, d_dens if ctx.needs_input_grad[1] else None, d_rgbs if ctx.needs_input_grad[2] else None, None, None
 
 

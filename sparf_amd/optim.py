@@ -63,15 +63,10 @@ class FusedAdam(torch.optim.Optimizer):
             arr = (ctypes.c_void_p * 20)(*[p.data_ptr() for p in params])
             b1, b2 = group["betas"]
             mg = group["max_grad_norm"]
-            with L.on(dev):
-                if self.device_step:      # (the host-side count above is then only informative: replays of a captured step do not pass here)
-                    L.check(lib.sparf_adam_step_dev(arr, L.ptr(flat), L.ptr(st["exp_avg"]), L.ptr(st["exp_avg_sq"]), L.ptr(st["ws"]), L.ptr(st["norm"]),
-                                                    float(group["lr"]), float(b1), float(b2), float(group["eps"]), L.ptr(st["step_dev"]),
-                                                    float(mg) if mg else 0.0, L.stream_ptr(dev)), "sparf_adam_step_dev")
-                else:
-                    L.check(lib.sparf_adam_step(arr, L.ptr(flat), L.ptr(st["exp_avg"]), L.ptr(st["exp_avg_sq"]), L.ptr(st["ws"]), L.ptr(st["norm"]),
-                                                float(group["lr"]), float(b1), float(b2), float(group["eps"]), int(st["step"]),
-                                                float(mg) if mg else 0.0, L.stream_ptr(dev)), "sparf_adam_step")
+            # the step count: the device's own counter, or the host's (then only informative: replays of a captured step do not pass here)
+            name, step = ("sparf_adam_step_dev", L.ptr(st["step_dev"])) if self.device_step else ("sparf_adam_step", int(st["step"]))
+            L.call(name, dev, arr, L.ptr(flat), L.ptr(st["exp_avg"]), L.ptr(st["exp_avg_sq"]), L.ptr(st["ws"]), L.ptr(st["norm"]), float(group["lr"]),
+                   float(b1), float(b2), float(group["eps"]), step, float(mg) if mg else 0.0)
             self._nets[gi].weights_changed()    # raw-pointer update: torch's version counters did not move
             self.last_grad_norms[gi] = st["norm"] if mg else None
         return loss

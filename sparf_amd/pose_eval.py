@@ -19,6 +19,7 @@ import torch
 from . import lib as L
 from .camera import invert_pose
 from .edict import EasyDict as edict
+from .patcher import Patcher
 
 MAX_POSES = L.POSE_EVAL_MAX_POSES        # of one set, in the kernel
 MAX_VIEWS = 10                           # joint_pose_nerf_trainer.py:233: the pairs of the first min(B, 10) views
@@ -209,8 +210,7 @@ def evaluate_poses(pose_w2c, pose_gt_w2c, align=True):
     a = L.PoseEval(pose=pose.data_ptr(), pose_gt=gt.data_ptr(), gt_sets=gt_sets, S=S, B=B, flags=L.POSE_EVAL_ALIGN if align else 0,
                    stats=stats.data_ptr(), errors=errors.data_ptr(), aligned=aligned.data_ptr(), sim3=packed.data_ptr(), best=best.data_ptr(),
                    scores=scores.data_ptr())
-    with L.on(dev):
-        L.check(L.load().sparf_pose_eval(ctypes.byref(a), L.stream_ptr(dev)), "sparf_pose_eval")
+    L.call("sparf_pose_eval", dev, ctypes.byref(a))
     return _result(stats, errors, aligned, best, scores[:, :n_pairs(B) if align else 0], packed, single)
 
 
@@ -223,7 +223,7 @@ def pack_sim3(sim3, device, dtype=torch.float32):
                       torch.as_tensor(sim3.s, device=device, dtype=dtype).reshape(1)])
 
 
-_originals = {}                  # the trainer's own methods and function, saved by install(): what the kernels do not take goes to them
+_installer = Patcher("sparf_amd.pose_eval.install", "uninstall")     # keeps the trainer's own methods and function: what the kernels do not take goes to them
 
 
 def backtrack(pose_gt_w2c, sim3):
@@ -238,8 +238,7 @@ def backtrack(pose_gt_w2c, sim3):
     packed = pack_sim3(sim3, dev).detach().contiguous()
     gt = pose_gt_w2c.detach().contiguous()
     out = torch.empty_like(gt)
-    with L.on(dev):
-        L.check(L.load().sparf_pose_backtrack(L.ptr(gt), gt.shape[0], L.ptr(packed), 0, L.ptr(out), L.stream_ptr(dev)), "sparf_pose_backtrack")
+    L.call("sparf_pose_backtrack", dev, L.ptr(gt), gt.shape[0], L.ptr(packed), 0, L.ptr(out))
     return out
 
 
@@ -296,12 +295,11 @@ def _evaluate_any_poses_torch(self, opt, pose_w2c, pose_GT_w2c):
 
 def _original_method(name, restatement):
     """the trainer's own method where install() saved one -- not inside unfused(), which asks for this file's restatement"""
-    return restatement if _unfused or name not in _originals else _originals[name]
+    return restatement if _unfused else _installer.original(name) or restatement
 
 
 METHODS = ("evaluate_camera_alignment", "prealign_w2c_small_camera_systems", "evaluate_any_poses")
 BACKTRACK = "backtrack_from_aligning_the_trajectory"
-_patched = []
 
 
 def install(pose_evaluation_class, *importing_modules):
@@ -309,28 +307,18 @@ def install(pose_evaluation_class, *importing_modules):
     (CommonPoseEvaluation of source.training.joint_pose_nerf_trainer; its subclasses inherit them) and `backtrack` under the name
     backtrack_from_aligning_the_trajectory on every module given that has it (align_trajectories itself, and joint_pose_nerf_trainer,
     which imported it by name), until `uninstall()`.  Nothing in this package calls it."""
-    if _patched:
-        raise RuntimeError("sparf_amd.pose_eval.install: already installed; call uninstall() first")
+    _installer.guard()
     ours = dict(evaluate_camera_alignment=evaluate_camera_alignment, prealign_w2c_small_camera_systems=prealign_w2c_small_camera_systems,
                 evaluate_any_poses=evaluate_any_poses)
     for name in METHODS:
-        own = name in vars(pose_evaluation_class)
         if hasattr(pose_evaluation_class, name):
-            _originals[name] = getattr(pose_evaluation_class, name)
-        _patched.append((pose_evaluation_class, name, own, vars(pose_evaluation_class).get(name)))
-        setattr(pose_evaluation_class, name, ours[name])
+            _installer.save(name, getattr(pose_evaluation_class, name))        # (inherited ones too)
+        _installer.put(pose_evaluation_class, name, ours[name])
     for mod in importing_modules:
         if BACKTRACK in vars(mod):
-            _originals.setdefault(BACKTRACK, vars(mod)[BACKTRACK])
-            _patched.append((mod, BACKTRACK, True, vars(mod)[BACKTRACK]))
-            setattr(mod, BACKTRACK, backtrack)
+            _installer.save(BACKTRACK, vars(mod)[BACKTRACK])                 # (the first one met stays)
+            _installer.put(mod, BACKTRACK, backtrack)
 
 
 def uninstall():
-    while _patched:
-        obj, name, own, old = _patched.pop()
-        if own:
-            setattr(obj, name, old)
-        else:
-            delattr(obj, name)
-    _originals.clear()
+    _installer.restore()

@@ -1,18 +1,15 @@
-"""A stand-in for the loaded library under ops.colmap_compact / ops.colmap_gather / ops.ColmapLoss (the pattern of tests/matches_fake.py),
-for tests that run the glue of the DS-NeRF sparse depth loss on CPU tensors: it launches nothing and records every call of the three
-entry points as (name, {argument: True / False for a pointer given / NULL, the integer}); the stream is left out.  `raw` holds the same
-calls with the addresses themselves, for tests of which tensor a pointer is.  The tensors are host memory here, so compact answers
+"""A stand-in for the loaded library under ops.colmap_compact / ops.colmap_gather / ops.ColmapLoss (tests/fake_lib.Recorder over
+the three entry points of the DS-NeRF sparse depth loss).  The tensors are host memory here, so compact answers
 through its `count` pointer with the counts of `valid` / `positive` (default: what tests/colmap_referee.py counts in the map behind the
 `depth` pointer) -- the glue's one readback then reads numbers --, gather fills its outputs from the maps as the kernel would, and loss
 writes 0.  The workspace query answers as the library does and is not recorded.
 Also here: DepthNet, the `net` of a loss module whose render is an exact function of the image and the ray list."""
-import contextlib
 import ctypes
 
 import numpy as np
 import torch
 
-from sparf_amd import lib as L
+from tests import fake_lib
 
 COLMAP_CALLS = {
     "sparf_colmap_compact": ("depth", "B", "H", "W", "index", "count", "workspace"),
@@ -32,33 +29,16 @@ def _array(address, n, dtype):
     return np.frombuffer((ctypes.c_char * size).from_address(address), dtype=dtype)
 
 
-class ColmapFakeLib:
+class ColmapFakeLib(fake_lib.Recorder):
     def __init__(self):
-        self.calls, self.raw = [], []
+        super().__init__(COLMAP_CALLS)
         self.valid = self.positive = None        # per-image counts compact reports (None: counted in the map)
 
     def sparf_colmap_workspace_bytes(self, B, n, rows):
         return workspace_bytes(B, n, rows)
 
-    def __getattr__(self, name):
-        if name not in COLMAP_CALLS:
-            raise AttributeError(name)           # the sparse depth loss enters nothing else
-
-        def call(*args):
-            names, types = COLMAP_CALLS[name], L.EXPORTS[name][1]
-            assert len(args) == len(types) == len(names) + 1, (name, len(args))
-            rec, raw = {}, {}
-            for n, t, v in zip(names, types, args):
-                if t is ctypes.c_void_p:
-                    v = v.value if isinstance(v, ctypes.c_void_p) else v
-                    rec[n], raw[n] = v is not None and v != 0, v
-                else:
-                    rec[n] = raw[n] = int(v)
-            self.calls.append((name, rec))
-            self.raw.append((name, raw))
-            getattr(self, "_" + name[len("sparf_colmap_"):])(raw)
-            return 0
-        return call
+    def after(self, name, raw, rec):
+        getattr(self, "_" + name[len("sparf_colmap_"):])(raw)
 
     def _compact(self, a):
         B, n = a["B"], a["H"] * a["W"]
@@ -92,23 +72,9 @@ class ColmapFakeLib:
             if a[k]:
                 _array(a[k], a["K"], np.float32)[:] = 0.0
 
-    def names(self):
-        return [c[0] for c in self.calls]
 
-
-@contextlib.contextmanager
 def installed():
-    lib = ColmapFakeLib()
-    fakes = [(L, "load", lambda: lib), (L, "require_gpu", lambda d: d), (L, "on", lambda d: contextlib.nullcontext()),
-             (L, "stream_ptr", lambda d: None)]
-    saved = [(obj, name, getattr(obj, name)) for obj, name, _ in fakes]
-    try:
-        for obj, name, f in fakes:
-            setattr(obj, name, f)
-        yield lib
-    finally:
-        for obj, name, real in saved:
-            setattr(obj, name, real)
+    return fake_lib.installed(ColmapFakeLib())
 
 
 class DepthNet:

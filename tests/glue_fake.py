@@ -8,13 +8,13 @@ nothing, sizes areas with the real library's host arithmetic, and records what t
 
 While the stand-in is installed every tensor whose address is taken stays alive (Tensor.data_ptr keeps it), so no address that
 reached the trace is handed out again within a test."""
-import contextlib
 import ctypes
 
 import pytest
 import torch
 
 from sparf_amd import lib as L
+from tests import fake_lib
 
 # the flat calls that are recorded, with their argument names (include/sparf_hip.h; the stream, last, is left out)
 FLAT_CALLS = {
@@ -78,7 +78,6 @@ class FakeLib:
         return 0
 
 
-@contextlib.contextmanager
 def installed():
     """-> the FakeLib, standing in for the library (and for the GPU checks, the device guard, the stream and the static tables of
     sparf_amd.lib) until the block ends"""
@@ -89,21 +88,9 @@ def installed():
         keep.append(t)
         return real_data_ptr(t)
 
-    fakes = [(L, "load", lambda: lib), (L, "require_gpu", lambda d: d), (L, "on", lambda d: contextlib.nullcontext()),
-             (L, "stream_ptr", lambda d: None),
-             (L, "tables_device", lambda prec, d: tables.setdefault((prec, str(d)), torch.zeros(4, dtype=torch.int32))),     # (cached per precision and device, as the real ones are)
-             (torch.Tensor, "data_ptr", data_ptr)]
-    saved = [(obj, name, vars(obj).get(name)) for obj, name, _ in fakes]
-    try:
-        for obj, name, f in fakes:
-            setattr(obj, name, f)
-        yield lib
-    finally:
-        for obj, name, real in saved:
-            if real is None:             # (inherited, Tensor.data_ptr: the class goes back to having none of its own)
-                delattr(obj, name)
-            else:
-                setattr(obj, name, real)
+    # (the tables: cached per precision and device, as the real ones are; Tensor.data_ptr is inherited: the class goes back to having none of its own)
+    return fake_lib.installed(lib, (L, "tables_device", lambda prec, d: tables.setdefault((prec, str(d)), torch.zeros(4, dtype=torch.int32))),
+                              (torch.Tensor, "data_ptr", data_ptr))
 
 
 @pytest.fixture

@@ -3,10 +3,10 @@ CPU tensors: it launches nothing and records every call of the entry point as a 
 (None for NULL), a stride array as a tuple, integers and the scale as they are; the stream is left out.  The tensors are host memory
 here, so the call answers through its `out` and `counts` pointers with recognisable numbers.  The workspace query answers as the
 library does and is not recorded."""
-import contextlib
 import ctypes
 
 from sparf_amd import lib as L
+from tests import fake_lib
 
 TH, TW, NACC = 16, 32, 18        # csrc/metrics.h METRICS_TH, METRICS_TW, METRICS_NACC
 OUT = tuple(float(i) + 0.5 for i in range(20))           # what a call leaves in out[2][10]
@@ -43,7 +43,6 @@ class MetricsFakeLib:
         raise AttributeError(name)               # the metrics functions enter nothing else
 
 
-@contextlib.contextmanager
 def installed():
     """the stand-in under sparf_amd.lib, and the route predicate of sparf_amd.metrics blind to the device (the tensors are on the CPU)"""
     from sparf_amd import metrics
@@ -68,13 +67,4 @@ def installed():
         def numel(self):
             return self.t.numel()
 
-    fakes = [(L, "load", lambda: lib), (L, "require_gpu", lambda d: d), (L, "on", lambda d: contextlib.nullcontext()),
-             (L, "stream_ptr", lambda d: None), (metrics, "_takes_kernel", takes)]
-    saved = [(obj, name, getattr(obj, name)) for obj, name, _ in fakes]
-    try:
-        for obj, name, f in fakes:
-            setattr(obj, name, f)
-        yield lib
-    finally:
-        for obj, name, real in saved:
-            setattr(obj, name, real)
+    return fake_lib.installed(lib, (metrics, "_takes_kernel", takes))

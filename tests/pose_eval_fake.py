@@ -2,10 +2,10 @@
 tensors: it launches nothing and records every call of the two entry points -- sparf_pose_eval as a dict of the struct's fields (a pointer
 as its address, None for NULL), sparf_pose_backtrack as a dict of its arguments; the stream is left out.  The tensors are host memory
 here, so a call answers through its output pointers with recognisable numbers."""
-import contextlib
 import ctypes
 
 from sparf_amd import lib as L
+from tests import fake_lib
 
 STATS = (0.5, 1.5, 2.5, 3.5)     # what a call leaves in every row of stats
 BEST = 1
@@ -45,19 +45,9 @@ class PoseEvalFakeLib:
         raise AttributeError(name)               # the pose-evaluation functions enter nothing else
 
 
-@contextlib.contextmanager
 def installed():
     """the stand-in under sparf_amd.lib, and the route predicate of sparf_amd.pose_eval blind to the device (the tensors are on the CPU)"""
     import torch
     from sparf_amd import pose_eval
-    lib = PoseEvalFakeLib()
-    fakes = [(L, "load", lambda: lib), (L, "require_gpu", lambda d: d), (L, "on", lambda d: contextlib.nullcontext()),
-             (L, "stream_ptr", lambda d: None), (pose_eval, "_on_device", lambda *ts: all(t.dtype == torch.float32 and t.layout == torch.strided for t in ts))]
-    saved = [(obj, name, getattr(obj, name)) for obj, name, _ in fakes]
-    try:
-        for obj, name, f in fakes:
-            setattr(obj, name, f)
-        yield lib
-    finally:
-        for obj, name, real in saved:
-            setattr(obj, name, real)
+    on_device = lambda *ts: all(t.dtype == torch.float32 and t.layout == torch.strided for t in ts)
+    return fake_lib.installed(PoseEvalFakeLib(), (pose_eval, "_on_device", on_device))

@@ -188,7 +188,7 @@ def test_method_before_the_start_iteration_and_with_distortion(fx, wants):
     finally:
         losses.uninstall_photometric()
     assert base.BasePhotoandReguLoss().compute_loss(None, None, None, 1) == ("theirs", 1, None)
-    assert trainer.compute_mse_on_rays(None, None) == "their mse" and trainer.other == 1 and not losses._original_photo
+    assert trainer.compute_mse_on_rays(None, None) == "their mse" and trainer.other == 1 and not losses._photo.originals
     # a module that had no such name loses it again
     bare = types.SimpleNamespace()
     losses.install_photometric(base, bare)

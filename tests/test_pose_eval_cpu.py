@@ -270,7 +270,7 @@ def test_install_and_uninstall_round_trip():
     finally:
         PE.uninstall()
     assert dict(vars(_Trainer)) == before and align_mod.backtrack_from_aligning_the_trajectory is original_backtrack
-    assert trainer_mod.backtrack_from_aligning_the_trajectory is original_backtrack and PE._originals == {} and PE._patched == []
+    assert trainer_mod.backtrack_from_aligning_the_trajectory is original_backtrack and PE._installer.originals == {} and PE._installer.patched == []
     PE.install(_Sub)                                           # a class without methods of its own goes back to having none
     PE.uninstall()
     assert not any(m in vars(_Sub) for m in PE.METHODS) and _Sub().evaluate_any_poses(None, 1, 2) == "original evaluate_any_poses"
