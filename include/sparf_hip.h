@@ -404,6 +404,40 @@ int sparf_colmap_loss(const float* target, const float* weight, const int32_t* c
                       const float* depth_fine /*NULL ok*/, float* out, float* d_depth /*NULL ok*/, float* d_depth_fine /*NULL ok*/,
                       void* workspace /*NULL ok*/, void* stream);
 
+/* ---- depth errors on rendered rays -------------------------------------------
+ * compute_depth_error_on_rays (source/training/core/metrics.py:81-134), which the trainers run
+ * once per head on every training iteration (nerf_trainer.py:307-325), as ONE call for both heads:
+ * no indexed copy of the maps, no index build, no boolean selection and so no readback.
+ * depth_gt [B_maps][HW] (float32) and valid [B_maps][HW] (bytes, torch.bool storage; NULL: every
+ *   row is kept) are the maps of the whole scene as stored, read in place.
+ * Row r of rendered image b (0 <= b < B, 0 <= r < N) reads map m = img_idx[b] (int64, device; NULL:
+ *   m = b), clamped to [0, B_maps), at pixel p = ray_idx[r] (per_image 0: one list for all images),
+ *   ray_idx[b][r] (per_image 1) or r itself (ray_idx NULL: full images, N == HW), clamped to
+ *   [0, HW).  An index outside its range is the caller's error (torch raises on it); the clamps
+ *   keep the launch inside the maps.  No address depends on a value read from a map.
+ * The row is kept if valid[m][p] != 0.  A kept row contributes |e| and e^2 with
+ *   e = depth_gt[m][p] - depth[b][r] s in double on the fp32 operands; s is scale_dev[0] (one float
+ *   in device memory) where scale_dev is given, else scale.  depth_fine (NULL ok) is a second
+ *   head on the same rows: the map and the mask are read once for both.
+ * out[4] = abs_e, rmse, abs_e_fine, rmse_fine with abs_e = sum |e| / (K + 1e-6) and
+ *   rmse = sqrt(sum e^2 / K) over the K kept rows, each rounded to float32 once; K == 0 gives
+ *   abs_e 0 and rmse NaN, as the reference's mean of an empty selection does; the fine pair is 0
+ *   without depth_fine.  count[0] = K.  B N == 0 gives that K == 0 result and reads no input.
+ * Sums in double in a fixed order (thread, wave butterfly, waves, chunks in chunk order), no
+ *   atomic, no workgroup waits for another: the same bits from call to call.
+ * workspace: sparf_ray_depth_err_workspace_bytes(B N) bytes (0 up to 4096 rows: one workgroup, one
+ *   launch; above, five doubles per chunk of 4096 rows and two launches; NULL = the one-workgroup
+ *   path at any size).
+ * Returns 1 before any HIP call for a negative size, B_maps <= 0, B HW or B N above 2^30,
+ * per_image outside {0, 1}, or, when there are rows, ray_idx NULL with N != HW (the empty index
+ * list of a call without rows has no address), a missing required pointer (depth_gt, depth, out,
+ * count) or HW == 0. */
+int64_t sparf_ray_depth_err_workspace_bytes(int64_t rows);
+int sparf_ray_depth_err(const float* depth_gt, const unsigned char* valid /*NULL ok*/, const int64_t* img_idx /*NULL ok*/,
+                        const int64_t* ray_idx /*NULL ok*/, int per_image, int B_maps, int B, int HW, int N,
+                        const float* depth, const float* depth_fine /*NULL ok*/, float scale, const float* scale_dev /*NULL ok*/,
+                        float* out, int32_t* count, void* workspace /*NULL ok*/, void* stream);
+
 /* ---- evaluation metrics ----------------------------------------------------
  * compute_metrics / compute_metrics_masked / compute_depth_error (source/training/core/metrics.py:
  * 136-268, called per head by source/training/base.py:475-499 and nerf_trainer.py:387-405) with the

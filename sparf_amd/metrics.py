@@ -7,6 +7,11 @@ operands that are not float32, one-channel images, a float mask, and `unfused()`
 `image_metrics` returns device tensors and reads nothing back.  `compute_metrics`, `compute_metrics_masked` and `ssim` carry the
 reference's own signatures, key names and return types; `install()` puts them under the reference's names on the modules that imported
 them.  LPIPS stays the caller's callable.  Nothing in this package calls install(); there is no `opt.hip` key.
+
+Depth errors on rendered rays: compute_depth_error_on_rays (metrics.py:81-134), what the trainers log on every
+training iteration, as ONE library call for both heads without a readback (ops.ray_depth_err: csrc/depth_err.hip) -- `depth_error_on_rays`,
+its restatement `depth_error_on_rays_torch`, `compute_depth_error_on_rays` under the reference's signature, and
+`install_depth_error_on_rays()` with a patcher of its own.
 """
 import contextlib
 import math
@@ -240,6 +245,144 @@ def compute_metrics(data_dict, output_dict, pred_rgb_map, pred_depth, gt_rgb_map
         lpips_masked = lpips_loss(rgb_map_fg * 2 - 1, gt_rgb_map_fg * 2 - 1).item()
         results.update({'psnr_masked' + suffix: v[4], 'ssim_masked' + suffix: v[5], 'lpips_masked' + suffix: lpips_masked})
     return results
+
+
+# ---------------------------------------------------------------------------------------------- depth errors on rendered rays
+# compute_depth_error_on_rays (metrics.py:81-134), what make_result_dict runs once per head on every training
+# iteration (nerf_trainer.py:307-325), as ONE library call for both heads (ops.ray_depth_err: csrc/depth_err.hip), with its restatement.
+def _rays_head_torch(depth_gt_maps, valid_maps, idx_img_rendered, ray_idx, pred_depth, scaling_factor_for_pred_depth):
+    """metrics.py:103-134 for one head, line by line, on the maps of the scene -> (abs_e, rmse, the selection)"""
+    B = len(idx_img_rendered)
+    depth_gt = depth_gt_maps[idx_img_rendered].view(B, -1, 1)
+    valid_depth = valid_maps[idx_img_rendered].view(B, -1)
+    pred_depth = pred_depth.view(B, -1, 1)
+    if ray_idx is not None:
+        if len(ray_idx.shape) == 2 and ray_idx.shape[0] == B:
+            n_rays = ray_idx.shape[-1]
+            batch_idx_flattened = torch.arange(start=0, end=B).unsqueeze(-1).repeat(1, n_rays).long().view(-1)
+            ray_idx_flattened = ray_idx.reshape(-1).long()
+            depth_gt = depth_gt[batch_idx_flattened, ray_idx_flattened]
+            depth_gt = depth_gt.reshape(B, n_rays, -1)
+            valid_depth = valid_depth[batch_idx_flattened, ray_idx_flattened]
+            valid_depth = valid_depth.reshape(B, n_rays, -1)
+        else:
+            depth_gt = depth_gt[:, ray_idx]
+            valid_depth = valid_depth[:, ray_idx]
+    depth_gt = depth_gt[valid_depth]
+    pred_depth = pred_depth[valid_depth] * scaling_factor_for_pred_depth
+    abs_e = torch.abs(depth_gt - pred_depth)
+    abs_e = abs_e.sum() / (abs_e.nelement() + 1e-6)
+    rmse = torch.sqrt((depth_gt - pred_depth).pow(2).mean())         # compute_rmse(depth_gt, pred_depth), metrics.py:78-79
+    return abs_e, rmse, valid_depth
+
+
+def _rays_maps(depth_gt, valid_depth_gt):
+    """the maps as data_dict holds them; without a mask every pixel is valid"""
+    if valid_depth_gt is None:
+        valid_depth_gt = torch.ones(depth_gt.shape, dtype=torch.bool, device=depth_gt.device)
+    return depth_gt, valid_depth_gt.reshape(depth_gt.shape).bool()
+
+
+def _rays_result(vector, count, fine):
+    """vector [4] / count [1] -> dict of 0-dim views: abs_e, rmse, with a fine head abs_e_fine, rmse_fine, and n_valid"""
+    res = edict(vector=vector, count=count)
+    for i, key in enumerate(ops.DEPTH_ERR_OUTS[:4 if fine else 2]):
+        res[key] = vector[i]
+    res.n_valid = count[0]
+    return res
+
+
+def depth_error_on_rays_torch(depth_gt, valid_depth_gt, depth, depth_fine=None, *, ray_idx=None, img_idx=None, scale=1.0):
+    """The torch restatement of depth_error_on_rays: the reference's lines in the reference's order, once per head, in the operands' own
+    dtype, with their indexed copies and the readbacks of their boolean selections.  -> the same dict; the float32 rounding of `vector`
+    is the only thing added."""
+    maps, valid = _rays_maps(depth_gt, valid_depth_gt)
+    idx = img_idx if img_idx is not None else torch.arange(depth.shape[0], device=depth_gt.device)
+    values, kept = [], None
+    for d in (depth, depth_fine):
+        if d is None:
+            values += [torch.zeros((), device=depth_gt.device, dtype=depth_gt.dtype)] * 2
+            continue
+        abs_e, rmse, kept = _rays_head_torch(maps, valid, idx, ray_idx, d, scale)
+        values += [abs_e, rmse]
+    vector = torch.stack([v.to(depth_gt.dtype) for v in values]).float()
+    return _rays_result(vector, kept.sum().to(torch.int32).reshape(1), depth_fine is not None)
+
+
+def _on_gpu(device):
+    return device.type == "cuda"
+
+
+def _rays_take_kernel(depth_gt, valid_depth_gt, depths, ray_idx, img_idx, scale):
+    """float32 maps and depths, a bool (or 0/1 byte) mask and int64 indices, all on one GPU, and no gradient asked of a depth"""
+    if _unfused:
+        return False
+    dev = depth_gt.device
+    here = lambda t, dtypes: t is None or (t.device == dev and t.layout == torch.strided and t.dtype in dtypes)
+    depths = [d for d in depths if d is not None]
+    if torch.is_grad_enabled() and any(d.requires_grad for d in depths):
+        return False
+    if torch.is_tensor(scale) and (scale.numel() != 1 or scale.is_complex()):
+        return False
+    B = depths[0].shape[0]
+    return (_on_gpu(dev) and all(here(t, (torch.float32,)) for t in (depth_gt, *depths)) and here(valid_depth_gt, (torch.bool, torch.uint8)) and
+            here(ray_idx, (torch.int64,)) and here(img_idx, (torch.int64,)) and
+            (ray_idx is None or ray_idx.dim() == 1 or (ray_idx.dim() == 2 and ray_idx.shape[0] == B)))
+
+
+def depth_error_on_rays(depth_gt, valid_depth_gt, depth, depth_fine=None, *, ray_idx=None, img_idx=None, scale=1.0):
+    """The depth errors of one or two rendered heads against the ground-truth maps of the scene, on the rendered rays only:
+    depth_gt [B_maps,H,W] or [B_maps,1,H,W] float32 and valid_depth_gt (bool, as many elements; None: every pixel) are read in place;
+    depth / depth_fine [B,N,1] or [B,N]; ray_idx int64 [N] (one list for all images), [B,N] (two-dimensional with shape[0] == B: one
+    list per image, the reference's rule) or None (full images); img_idx int64 [B] on the device names the map of each rendered image
+    (None: the first B maps in order); scale a Python or numpy number or a one-element tensor (one on the GPU is never read back).
+    -> dict of 0-dim device tensors abs_e, rmse, with depth_fine abs_e_fine, rmse_fine, and n_valid (int32): views of `vector` [4]
+    and `count` [1].  One kernel call, no readback.  Another dtype, a tensor off the GPU, `unfused()` or a gradient asked of a depth
+    take depth_error_on_rays_torch."""
+    if not _rays_take_kernel(depth_gt, valid_depth_gt, (depth, depth_fine), ray_idx, img_idx, scale):
+        return depth_error_on_rays_torch(depth_gt, valid_depth_gt, depth, depth_fine, ray_idx=ray_idx, img_idx=img_idx, scale=scale)
+    vector, count = ops.ray_depth_err(depth_gt, valid_depth_gt, depth, depth_fine, ray_idx, img_idx, scale)
+    return _rays_result(vector, count, depth_fine is not None)
+
+
+def compute_depth_error_on_rays(data_dict, output_dict, pred_depth, scaling_factor_for_pred_depth=1.):
+    """metrics.py:81-134 under its own signature: (abs_e, rmse) as 0-dim tensors for the one head it is given.  One kernel call and no
+    readback: output_dict.idx_img_rendered goes to the kernel as it is where it is a device tensor; a host list is uploaded, unless it
+    names every rendered image in order (then the kernel needs no index)."""
+    idx = output_dict.idx_img_rendered
+    ray_idx = output_dict.ray_idx if 'ray_idx' in output_dict.keys() else None
+    depth_gt, valid = data_dict.depth_gt, data_dict.valid_depth_gt
+    B = len(idx)
+    on_host = not torch.is_tensor(idx) or (idx.device.type == "cpu" and idx.device != depth_gt.device)
+    if not _rays_take_kernel(depth_gt, valid, (pred_depth,), ray_idx, None if on_host else idx, scaling_factor_for_pred_depth) or pred_depth.shape[0] != B:
+        abs_e, rmse, _ = _rays_head_torch(depth_gt, valid, idx, ray_idx, pred_depth, scaling_factor_for_pred_depth)
+        return abs_e, rmse
+    if on_host:
+        listed = [int(i) for i in idx]
+        idx = None if listed == list(range(B)) else torch.tensor(listed, dtype=torch.int64, device=depth_gt.device)
+    vector, _ = ops.ray_depth_err(depth_gt, valid, pred_depth, None, ray_idx, idx, scaling_factor_for_pred_depth)
+    return vector[0], vector[1]
+
+
+_rays_installer = Patcher("sparf_amd.metrics.install_depth_error_on_rays", "uninstall_depth_error_on_rays")
+RAYS_NAME = "compute_depth_error_on_rays"
+
+
+def install_depth_error_on_rays(metrics_module, *importing_modules):
+    """Opt-in, and independent of install(): put compute_depth_error_on_rays above under that name on `metrics_module`
+    (source.training.core.metrics) and on every module given whose own namespace holds the name (nerf_trainer imports it by name),
+    until `uninstall_depth_error_on_rays()`.  Nothing in this package calls it."""
+    _rays_installer.guard()
+    if hasattr(metrics_module, RAYS_NAME):
+        _rays_installer.save(RAYS_NAME, getattr(metrics_module, RAYS_NAME))
+    _rays_installer.put(metrics_module, RAYS_NAME, compute_depth_error_on_rays)
+    for mod in importing_modules:
+        if RAYS_NAME in vars(mod):
+            _rays_installer.put(mod, RAYS_NAME, compute_depth_error_on_rays)
+
+
+def uninstall_depth_error_on_rays():
+    _rays_installer.restore()
 
 
 def install(metrics_module, *importing_modules):

@@ -1302,6 +1302,78 @@ def image_metrics(pred, gt, pred_fine=None, fg_mask=None, depth=None, depth_fine
     return out, counts
 
 
+# ---------------------------------------------------------------------------------------------- depth errors on rendered rays
+# compute_depth_error_on_rays (metrics.py:81-134), both heads.  A plain function: the reference runs it under no_grad.
+DEPTH_ERR_OUTS = ("abs_e", "rmse", "abs_e_fine", "rmse_fine")            # csrc/depth_err.h
+
+
+def _depth_err_rows(t, B, name):
+    """a rendered depth [B,N,1] or [B,N] float32 -> dense [B,N]"""
+    if t.dtype != torch.float32 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 1) or t.shape[0] != B:
+        raise ValueError(f"depth error on rays: {name} must be float32 [{B},N,1] or [{B},N], got {t.dtype} {list(t.shape)}")
+    return t.detach().reshape(B, t.numel() // B if B else 0).contiguous()
+
+
+def ray_depth_err(depth_gt, valid_depth_gt, depth, depth_fine=None, ray_idx=None, img_idx=None, scale=1.0):
+    """sparf_ray_depth_err: depth_gt float32 [B_maps,H,W] or [B_maps,1,H,W] and valid_depth_gt (torch.bool or 0/1 bytes, as many
+    elements; None: every pixel) are the maps of the scene, read in place (only another layout is copied); depth / depth_fine float32
+    [B,N,1] or [B,N]; ray_idx int64 [N] (one list for all images) or [B,N], None for full images; img_idx int64 [B] on the device: the
+    map of each rendered image, None for the first B maps in order; scale a number, or a one-element tensor -- on the operands' device
+    it is passed by pointer (converted there if it is not float32) and never read back, a host tensor is rounded to float32 on the host.
+    -> (out [4] float32: abs_e, rmse, abs_e_fine, rmse_fine -- the fine pair 0 without depth_fine; count [1] int32: the valid rows), on
+    the device: one library call, no readback"""
+    op = "depth error on rays"
+    if depth_gt.dtype != torch.float32 or depth_gt.dim() not in (3, 4) or (depth_gt.dim() == 4 and depth_gt.shape[1] != 1) or depth_gt.shape[0] < 1:
+        raise ValueError(f"{op}: depth_gt must be float32 [B,1,H,W] or [B,H,W] of at least one map, got {depth_gt.dtype} {list(depth_gt.shape)}")
+    dev = depth_gt.device
+    L.require_gpu(dev)
+    B_maps, HW = depth_gt.shape[0], depth_gt.shape[-2] * depth_gt.shape[-1]
+    gt = depth_gt.detach()
+    gt = gt if gt.is_contiguous() else gt.contiguous()
+    valid = None
+    if valid_depth_gt is not None:
+        if valid_depth_gt.dtype not in (torch.bool, torch.uint8) or valid_depth_gt.numel() != B_maps * HW:
+            raise ValueError(f"{op}: valid_depth_gt must be torch.bool with one element per pixel of depth_gt, got {valid_depth_gt.dtype} "
+                             f"{list(valid_depth_gt.shape)}")
+        valid = valid_depth_gt.detach()
+        valid = valid if valid.is_contiguous() else valid.contiguous()
+    B = depth.shape[0]
+    d = _depth_err_rows(depth, B, "depth")
+    N = d.shape[1]
+    df = None
+    if depth_fine is not None:
+        df = _depth_err_rows(depth_fine, B, "depth_fine")
+        if df.shape != d.shape:
+            raise ValueError(f"{op}: depth_fine has {list(depth_fine.shape)} for a depth of {list(depth.shape)}")
+    per_image = 0
+    if ray_idx is not None:
+        if ray_idx.dtype != torch.int64 or tuple(ray_idx.shape) not in ((N,), (B, N)):
+            raise ValueError(f"{op}: ray_idx must be int64 [{N}] or [{B}, {N}], got {ray_idx.dtype} {list(ray_idx.shape)}")
+        per_image = int(ray_idx.dim() == 2)
+        ray_idx = ray_idx.detach().contiguous()
+    elif N != HW:
+        raise ValueError(f"{op}: without ray_idx the render is of full images: {N} rays for {HW} pixels")
+    if img_idx is not None:
+        if img_idx.dtype != torch.int64 or img_idx.numel() != B:
+            raise ValueError(f"{op}: img_idx must be int64 [{B}], got {img_idx.dtype} {list(img_idx.shape)}")
+        img_idx = img_idx.detach().reshape(-1).contiguous()
+    scale_dev = None
+    if torch.is_tensor(scale):
+        if scale.numel() != 1:
+            raise ValueError(f"{op}: the scale must be one number, got {list(scale.shape)}")
+        s32 = scale.detach().reshape(1).to(torch.float32)
+        scale_dev, scale = (s32, 1.0) if s32.device == dev else (None, float(s32))
+    out = torch.empty(len(DEPTH_ERR_OUTS), device=dev, dtype=torch.float32)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    ws = L.workspace(L.load().sparf_ray_depth_err_workspace_bytes(B * N), dev, torch.float64)
+    p = L.ptr
+    # (a fine head without rows is an empty tensor and has no address: `out` marks it present -- a call without rows reads no input)
+    fine = p(out) if df is not None and df.numel() == 0 else p(df)
+    L.call("sparf_ray_depth_err", dev, p(gt), p(valid), p(img_idx), p(ray_idx), per_image, B_maps, B, HW, N, p(d), fine, float(scale), p(scale_dev),
+           p(out), p(count), p(ws))
+    return out, count
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
 class Composite(torch.autograd.Function):
     """NeRF.composite (frequency_nerf.py:283-343) on caller-built per-sample values (C ABI 6 sparf_composite_forward / _backward):
