@@ -1,8 +1,6 @@
 // C ABI of libsparf_hip.so (see include/sparf_hip.h): argument checking, workspace
 // carving and kernel sequencing on the caller's stream.  No allocation, no global state.
 #include "pass_plan.h"
-#include "reproj.h"
-#include "dcons.h"
 
 namespace sparf {
 int build_tables(int prec, int32_t* out);
@@ -22,16 +20,6 @@ int launch_pose_d9_bwd(const float* d9, int invert, int n, const float* d_pose, 
 int launch_pose_eval(const float* pose, const float* pose_gt, int gt_sets, int S, int B, int align, float* stats, float* errors, float* aligned,
                      float* sim3, int* best, float* scores, hipStream_t s);
 int launch_pose_backtrack(const float* pose_gt_w2c, int n, const float* sim3, int sim3_stride, float* out, hipStream_t s);
-// reproj.hip: n > 0
-int64_t reproj_workspace_bytes(int n);
-int launch_reproj(const ReprojArgs& a, hipStream_t s);
-// dcons.hip: n > 0
-int64_t dcons_workspace_bytes(int n);
-int launch_dcons_project(const DconsProjectArgs& a, hipStream_t s);
-int launch_dcons_project_bwd(const DconsProjectArgs& a, hipStream_t s);
-int launch_dcons_select(const DconsSelectArgs& a, hipStream_t s);
-int launch_dcons_select_bwd(const int32_t* dst, const float* d_uv, const float* d_z, int n, float* d_uv_in, float* d_z_in, hipStream_t s);
-int launch_dcons_loss(const DconsLossArgs& a, hipStream_t s);
 }  // namespace sparf
 
 using namespace sparf;
@@ -193,141 +181,6 @@ int sparf_pose_backtrack(const float* pose_gt_w2c, int n, const float* sim3, int
     if (n == 0) return 0;
     if (n < 0 || sim3_stride < 0 || !pose_gt_w2c || !sim3 || !out) return 1;
     return launch_pose_backtrack(pose_gt_w2c, n, sim3, sim3_stride, out, (hipStream_t)stream);
-}
-
-// ---- correspondence loss (sparf_hip.h): every argument check comes before any HIP call; n == 0 launches no kernel
-static inline bool reproj_opts_ok(int n, int loss_type, const float* out) {
-    return n >= 0 && n <= (1 << 30) && loss_type >= 0 && loss_type < REPROJ_LOSS_TYPES && out;
-}
-static int reproj_zero(float* p, int floats, hipStream_t s) {
-    return !p || hipMemsetAsync(p, 0, (size_t)floats * sizeof(float), s) == hipSuccess ? 0 : 2;
-}
-int64_t sparf_reproj_workspace_bytes(int n) { return reproj_workspace_bytes(n); }
-// corres_loss.py:50-95 compute_render_and_repro_loss_w_repro_thres: batched_geometry_utils.py:199-228 batch_project_to_other_img,
-// the two detached checks, base_losses.py:197-224 compute_diff_loss -- and what autograd derives from them for depth_i and T
-int sparf_reproj_loss(const float* pixels_i, const float* depth_i, const float* K_i, const float* pixels_j, const float* depth_j,
-                      const float* K_j, const float* T_itoj, const float* weights, int n, int loss_type, int pix_check, float pix_thresh,
-                      int depth_check, float depth_thresh, float* out, float* d_depth_i, float* d_T, unsigned char* valid, void* workspace,
-                      void* stream) {
-    if (!reproj_opts_ok(n, loss_type, out) || (depth_check && !depth_j)) return 1;
-    if (n > 0 && (!pixels_i || !depth_i || !K_i || !pixels_j || !K_j || !T_itoj)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (n == 0) return reproj_zero(out, 4, s) | reproj_zero(d_T, 16, s);
-    ReprojArgs a{};
-    a.n = n; a.nterms = 1; a.loss_type = loss_type; a.pix_check = pix_check != 0; a.depth_check = depth_check != 0; a.pair = 0;
-    a.pix_thresh = pix_thresh; a.depth_thresh = depth_thresh;
-    a.K[0] = K_i; a.K[1] = K_j; a.T = T_itoj; a.weights = weights;
-    a.term[0] = ReprojTerm{pixels_i, depth_i, pixels_j, depth_j, d_depth_i, 0, 1, 0};
-    a.out = out; a.valid = valid; a.d_T = d_T; a.ws = (double*)workspace;
-    return launch_reproj(a, s);
-}
-// corres_loss.py:183-219 of compute_loss_on_image_pair: T_self2other = P_other pose_inverse_4x4(P_self) (camera.py:37-61), its inverse,
-// the two (four with depth_fine) terms, their mean, stats_dict as that call order leaves it -- and the gradients to every depth and
-// to both poses
-int sparf_reproj_pair_loss(const float* pixels_self, const float* pixels_other, const float* depth_self, const float* depth_other,
-                           const float* depth_fine_self, const float* depth_fine_other, const float* K_self, const float* K_other,
-                           const float* pose_self, const float* pose_other, const float* weights, int n, int loss_type, int pix_check,
-                           float pix_thresh, int depth_check, float depth_thresh, float* out, float* d_depth_self, float* d_depth_other,
-                           float* d_depth_fine_self, float* d_depth_fine_other, float* d_pose_self, float* d_pose_other, void* workspace,
-                           void* stream) {
-    if (!reproj_opts_ok(n, loss_type, out)) return 1;
-    if ((depth_fine_self != nullptr) != (depth_fine_other != nullptr)) return 1;
-    if (!depth_fine_self && (d_depth_fine_self || d_depth_fine_other)) return 1;
-    if (n > 0 && (!pixels_self || !pixels_other || !depth_self || !depth_other || !K_self || !K_other || !pose_self || !pose_other)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (n == 0) return reproj_zero(out, 4, s) | reproj_zero(d_pose_self, 12, s) | reproj_zero(d_pose_other, 12, s);
-    ReprojArgs a{};
-    a.n = n; a.nterms = depth_fine_self ? 4 : 2; a.loss_type = loss_type; a.pix_check = pix_check != 0; a.depth_check = depth_check != 0; a.pair = 1;
-    a.pix_thresh = pix_thresh; a.depth_thresh = depth_thresh;
-    a.K[0] = K_self; a.K[1] = K_other; a.pose[0] = pose_self; a.pose[1] = pose_other; a.weights = weights;
-    a.term[0] = ReprojTerm{pixels_self, depth_self, pixels_other, depth_other, d_depth_self, 0, 1, 0};
-    a.term[1] = ReprojTerm{pixels_other, depth_other, pixels_self, depth_self, d_depth_other, 1, 0, 1};
-    a.term[2] = ReprojTerm{pixels_self, depth_fine_self, pixels_other, depth_fine_other, d_depth_fine_self, 0, 1, 0};
-    a.term[3] = ReprojTerm{pixels_other, depth_fine_other, pixels_self, depth_fine_self, d_depth_fine_other, 1, 0, 1};
-    a.out = out; a.d_pose[0] = d_pose_self; a.d_pose[1] = d_pose_other; a.ws = (double*)workspace;
-    return launch_reproj(a, s);
-}
-
-// ---- depth-consistency loss (sparf_hip.h): every argument check comes before any HIP call; n == 0 launches no kernel
-static inline bool dcons_n_ok(int n) { return n >= 0 && n <= (1 << 30); }
-static inline bool dcons_rows_ok(int rows) { return rows == 3 || rows == 4; }
-// 0: the points form, 1: the back-projecting form, -1: neither or both (or half of the second)
-static int dcons_form(const float* points_w, const float* pixels_ref, const float* depth_ref, const float* K_ref, const float* pose_c2w_ref, int ref_rows) {
-    const int given = (pixels_ref != nullptr) + (depth_ref != nullptr) + (K_ref != nullptr) + (pose_c2w_ref != nullptr);
-    if (points_w) return given == 0 ? 0 : -1;
-    return given == 4 && dcons_rows_ok(ref_rows) ? 1 : -1;
-}
-static int dcons_zero_count(int32_t* count, hipStream_t s) { return hipMemsetAsync(count, 0, sizeof(int32_t), s) == hipSuccess ? 0 : 2; }
-int64_t sparf_dcons_workspace_bytes(int n) { return n > 0 ? dcons_workspace_bytes(n) : 0; }
-// depth_cons_loss.py:247-259 (optionally with :209 folded in): batched_geometry_utils.py:244-247 batch_backproject_to_3d, :262-265
-// batch_project, the five-way mask and its boolean-index selections as one ordered compaction
-int sparf_dcons_project(const float* points_w, const float* pixels_ref, const float* depth_ref, const float* K_ref, const float* pose_c2w_ref,
-                        int ref_rows, const float* pose_w2c_unseen, int unseen_rows, const float* K_unseen, int n, int H, int W, float depth_min,
-                        const float* depth_min_dev, float* uv, float* z, int32_t* dst, int32_t* src, int32_t* count, void* workspace, void* stream) {
-    if (!dcons_n_ok(n) || !count || !dcons_rows_ok(unseen_rows)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (n == 0) return dcons_zero_count(count, s);       // (an empty tensor has no address: the pointers are not looked at)
-    if (dcons_form(points_w, pixels_ref, depth_ref, K_ref, pose_c2w_ref, ref_rows) < 0) return 1;
-    if (!pose_w2c_unseen || !K_unseen || !uv || !z || !dst || !src) return 1;
-    DconsProjectArgs a{};
-    a.n = n; a.ref_rows = ref_rows; a.unseen_rows = unseen_rows;
-    a.u_max = (float)(W - 1); a.v_max = (float)(H - 1); a.depth_min = depth_min; a.depth_min_dev = depth_min_dev;
-    a.points_w = points_w; a.pixels_ref = pixels_ref; a.depth_ref = depth_ref; a.K_ref = K_ref; a.pose_c2w_ref = pose_c2w_ref;
-    a.pose_w2c_unseen = pose_w2c_unseen; a.K_unseen = K_unseen;
-    a.uv = uv; a.z = z; a.dst = dst; a.src = src; a.count = count; a.ws = (int32_t*)workspace;
-    return launch_dcons_project(a, s);
-}
-// what autograd derives from the lines above for the world points, or for depth_ref in the back-projecting form: a gather through dst
-int sparf_dcons_project_backward(const float* points_w, const float* pixels_ref, const float* depth_ref, const float* K_ref,
-                                 const float* pose_c2w_ref, int ref_rows, const float* pose_w2c_unseen, int unseen_rows, const float* K_unseen,
-                                 int n, const int32_t* dst, const float* d_uv, const float* d_z, float* d_points_w, float* d_depth_ref,
-                                 void* stream) {
-    if (!dcons_n_ok(n) || !dcons_rows_ok(unseen_rows)) return 1;
-    if (n == 0) return 0;
-    const int form = dcons_form(points_w, pixels_ref, depth_ref, K_ref, pose_c2w_ref, ref_rows);
-    if (form < 0 || !pose_w2c_unseen || !K_unseen || !dst) return 1;
-    if (form == 0 ? (!d_points_w || d_depth_ref) : (!d_depth_ref || d_points_w)) return 1;
-    DconsProjectArgs a{};
-    a.n = n; a.ref_rows = ref_rows; a.unseen_rows = unseen_rows;
-    a.points_w = points_w; a.pixels_ref = pixels_ref; a.depth_ref = depth_ref; a.K_ref = K_ref; a.pose_c2w_ref = pose_c2w_ref;
-    a.pose_w2c_unseen = pose_w2c_unseen; a.K_unseen = K_unseen;
-    a.dst_in = dst; a.d_uv = d_uv; a.d_z = d_z; a.d_points_w = d_points_w; a.d_depth_ref = d_depth_ref;
-    return launch_dcons_project_bwd(a, (hipStream_t)stream);
-}
-// depth_cons_loss.py:277-283: valid_mask = visibility_weight_.ge(0.2) and its five selections
-int sparf_dcons_select(const float* vis, const float* uv, const float* z, int m, float thresh, float* uv_out, float* z_out, float* vis_out,
-                       int32_t* dst, int32_t* src, int32_t* count, void* workspace, void* stream) {
-    if (!dcons_n_ok(m) || !count) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (m == 0) return dcons_zero_count(count, s);
-    if (!vis || !uv || !z || !uv_out || !z_out || !vis_out || !dst || !src) return 1;
-    DconsSelectArgs a{};
-    a.n = m; a.thresh = thresh; a.vis = vis; a.uv = uv; a.z = z; a.uv_out = uv_out; a.z_out = z_out; a.vis_out = vis_out;
-    a.dst = dst; a.src = src; a.count = count; a.ws = (int32_t*)workspace;
-    return launch_dcons_select(a, s);
-}
-int sparf_dcons_select_backward(const int32_t* dst, const float* d_uv, const float* d_z, int m, float* d_uv_in, float* d_z_in, void* stream) {
-    if (!dcons_n_ok(m)) return 1;
-    if (m == 0) return 0;
-    if (!dst) return 1;
-    if (!d_uv_in && !d_z_in) return 0;
-    return launch_dcons_select_bwd(dst, d_uv, d_z, m, d_uv_in, d_z_in, (hipStream_t)stream);
-}
-// depth_cons_loss.py:293-312: the weighted compute_diff_loss (base_losses.py:197-224) of the coarse and, if given, the fine depth,
-// avg_vis_weight, and the gradient seeds of the pseudo depth and of both rendered depths
-int sparf_dcons_loss(const float* z_pseudo, const float* vis, const float* depth, const float* opacity, const float* depth_fine,
-                     const float* opacity_fine, int m, int loss_type, float* out, float* d_z_pseudo, float* d_depth, float* d_depth_fine,
-                     void* workspace, void* stream) {
-    if (!dcons_n_ok(m) || loss_type < 0 || loss_type >= DCONS_LOSS_TYPES || !out) return 1;
-    if ((depth_fine != nullptr) != (opacity_fine != nullptr) || (d_depth_fine && !depth_fine)) return 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (m == 0) return reproj_zero(out, 2, s);
-    if (!z_pseudo || !vis || !depth || !opacity) return 1;
-    DconsLossArgs a{};
-    a.n = m; a.loss_type = loss_type; a.z_pseudo = z_pseudo; a.vis = vis; a.depth = depth; a.opacity = opacity;
-    a.depth_fine = depth_fine; a.opacity_fine = opacity_fine; a.out = out;
-    a.d_z_pseudo = d_z_pseudo; a.d_depth = d_depth; a.d_depth_fine = d_depth_fine; a.ws = (double*)workspace;
-    return launch_dcons_loss(a, s);
 }
 
 int64_t sparf_adam_workspace_floats(void) { return 256; }

@@ -2,17 +2,17 @@
 // renders -- per image a torch.where with a host readback, six index and gather operations and two weighted means, and one more
 // torch.where over all images -- as three calls: compact (the valid pixels of every image in torch.where's order, their number and the
 // number of positive pixels), gather (the selected rows of every image, packed in image order) and loss (the value and both gradient
-// seeds).  The logic of a pixel and of a row is colmap.h's; this file owns the ordered compaction, the gather, the sums and the entry points.
+// seeds).  The logic of a pixel and of a row is colmap.h's; this file owns the item of the compaction, the gather, the loss loop and the entry points.
 //
-// Compaction: B images at once, the image is the grid's y dimension.  It keeps row-major order and uses no atomics (ordered.h:
-// ordered_compact_range, in tiles of COLMAP_BLOCK consecutive pixels, with the positive pixels as a second, counted flag).  Up to
+// Compaction: B images at once, the image is the grid's y dimension.  It keeps row-major order and uses no atomics (ordered.h's chunked
+// compaction over ColmapItem, in tiles of COLMAP_BLOCK consecutive pixels, with the positive pixels as a second, counted flag).  Up to
 // COLMAP_CHUNK pixels one workgroup per image does all of it in one launch; above, a counts launch over chunks of COLMAP_CHUNK pixels
 // and a write launch in which each workgroup adds the counts of the chunks before it in chunk order.  `count` stays in device memory;
 // the host reads its 2 B ints once.
 // Gather: one thread per selected row; the maps are read in place.  Every address comes from the index list and the device counts --
 // clamped against the count and the image size -- and none from a value read out of a map.
-// Loss: double arithmetic on the fp32 operands, one rounding per stored value.  Sums are fixed-order (ordered.h: block_totals,
-// sum_parts): a thread adds its rows in index order, then the wave, the waves and the chunks in their order: the same bits from call to call.
+// Loss: double arithmetic on the fp32 operands, one rounding per stored value.  Sums are fixed-order (ordered.h's chunked sum over
+// ColmapLossSum): a thread adds its rows in index order, then the wave, the waves and the chunks in their order: the same bits from call to call.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sparf_hip.h"
@@ -21,14 +21,18 @@
 
 namespace sparf {
 
-static constexpr int COLMAP_WAVES = COLMAP_BLOCK / 64;
-
-// what is compacted (the item of ordered_compact_range): the valid pixels of image b, their flat indices as the rows; the positive
-// pixels are counted along.  run[] = {valid, positive}.
+// what is compacted (the item of ordered.h's chunked compaction, B images): the valid pixels of image b, their flat indices as the rows;
+// the positive pixels are counted along.  run[] = {valid, positive}; `finish` leaves both as the image's counts.
 struct ColmapItem {
+    typedef ColmapCompactArgs Args;
+    typedef OrderedNoShared Shared;
+    static constexpr int BLOCK = COLMAP_BLOCK, CHUNK = COLMAP_CHUNK, NCOUNT = 2;
+    static __host__ __device__ int n(const ColmapCompactArgs& a) { return a.n; }
+    static __host__ __device__ int32_t* ws(const ColmapCompactArgs& a) { return a.ws; }
     const float* depth;
     int32_t* index;
-    __device__ ColmapItem(const ColmapCompactArgs& a, int b) : depth(a.depth + (size_t)b * (size_t)a.n), index(a.index + (size_t)b * (size_t)a.n) {}
+    __device__ ColmapItem(const ColmapCompactArgs& a, const OrderedNoShared*, int b)
+        : depth(a.depth + (size_t)b * (size_t)a.n), index(a.index + (size_t)b * (size_t)a.n) {}
     __device__ void flags(int p, bool in, bool (&f)[2]) const {
         const float d = in ? depth[p] : 0.0f;            // one guarded read for both flags
         f[0] = in & colmap_valid(d);
@@ -36,53 +40,11 @@ struct ColmapItem {
     }
     __device__ void place(int p, int j) const { index[j] = p; }
     __device__ void mark(int, int) const {}
+    static __device__ void finish(const ColmapCompactArgs& a, int b, const int (&run)[2]) {
+        a.count[b] = run[0];
+        a.count[a.B + b] = run[1];
+    }
 };
-
-static __device__ void colmap_counts(const ColmapCompactArgs& a, int b, const int (&run)[2]) {
-    a.count[b] = run[0];
-    a.count[a.B + b] = run[1];
-}
-
-// n <= COLMAP_CHUNK (or no workspace): one workgroup per image, every tile in turn
-__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_single_kernel(ColmapCompactArgs a) {
-    __shared__ int wave_tot[COLMAP_WAVES][2];
-    const int b = (int)blockIdx.y;
-    ColmapItem item(a, b);
-    int run[2] = {0, 0};
-    ordered_compact_range<COLMAP_BLOCK>(item, 0, a.n, true, run, wave_tot);
-    if (threadIdx.x == 0) colmap_counts(a, b, run);
-}
-
-// n > COLMAP_CHUNK, one workgroup per chunk and image: the valid and the positive pixels of chunk c of image b at ws[b][c]
-__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_counts_kernel(ColmapCompactArgs a) {
-    __shared__ int wave_tot[COLMAP_WAVES][2];
-    const int b = (int)blockIdx.y, first = (int)blockIdx.x * COLMAP_CHUNK;
-    ColmapItem item(a, b);
-    int run[2] = {0, 0};
-    ordered_compact_range<COLMAP_BLOCK>(item, first, min(a.n, first + COLMAP_CHUNK), false, run, wave_tot);
-    if (threadIdx.x == 0) {
-        int32_t* ws = a.ws + 2 * ((size_t)b * (size_t)a.chunks + blockIdx.x);
-        ws[0] = run[0];
-        ws[1] = run[1];
-    }
-}
-
-// same grid: every workgroup adds the counts of the chunks before it in chunk order and writes its chunk; the last one of an image
-// leaves the image's two counts
-__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_compact_write_kernel(ColmapCompactArgs a) {
-    __shared__ int wave_tot[COLMAP_WAVES][2];
-    const int b = (int)blockIdx.y, first = (int)blockIdx.x * COLMAP_CHUNK;
-    const int32_t* ws = a.ws + 2 * (size_t)b * (size_t)a.chunks;
-    ColmapItem item(a, b);
-    int base = 0, pos = 0;
-    for (int c = 0; c < (int)blockIdx.x; ++c) {
-        base += ws[2 * c];
-        pos += ws[2 * c + 1];
-    }
-    int run[2] = {base, pos};
-    ordered_compact_range<COLMAP_BLOCK>(item, first, min(a.n, first + COLMAP_CHUNK), true, run, wave_tot);
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) colmap_counts(a, b, run);
-}
 
 // base_losses.py:378-386 for row j of image b: the pixel behind the j-th selected entry of the image's index list, and what the two
 // maps hold there
@@ -118,31 +80,15 @@ static __device__ double colmap_loss_loop(const ColmapLossArgs& a, int first, in
     return acc;
 }
 
-// K <= COLMAP_CHUNK (or no workspace): one workgroup
-__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_loss_single_kernel(ColmapLossArgs a) {
-    __shared__ double red[COLMAP_WAVES][1];
-    const double acc = colmap_loss_loop(a, threadIdx.x, a.K);
-    double tot;
-    block_totals<1, COLMAP_WAVES>(&acc, red, &tot);
-    if (threadIdx.x == 0) a.out[0] = (float)colmap_total(tot, a.B);
-}
-// K > COLMAP_CHUNK, one workgroup per chunk of rows: its total at ws[chunk]
-__global__ void __launch_bounds__(COLMAP_BLOCK) colmap_loss_partial_kernel(ColmapLossArgs a) {
-    __shared__ double red[COLMAP_WAVES][1];
-    const int first = (int)blockIdx.x * COLMAP_CHUNK;
-    const double acc = colmap_loss_loop(a, first + (int)threadIdx.x, min(a.K, first + COLMAP_CHUNK));
-    double tot;
-    block_totals<1, COLMAP_WAVES>(&acc, red, &tot);
-    if (threadIdx.x == 0) a.ws[blockIdx.x] = tot;
-}
-// the partial totals added in chunk order
-__global__ void colmap_loss_finish_kernel(ColmapLossArgs a, int chunks) {
-    double tot;
-    sum_parts<1>(a.ws, chunks, &tot);
-    a.out[0] = (float)colmap_total(tot, a.B);
-}
-
-static inline int64_t colmap_chunks(int64_t n) { return (n + COLMAP_CHUNK - 1) / COLMAP_CHUNK; }
+// the policy of ordered.h's chunked sum: one total
+struct ColmapLossSum {
+    typedef ColmapLossArgs Args;
+    static constexpr int BLOCK = COLMAP_BLOCK, CHUNK = COLMAP_CHUNK, NACC = 1;
+    static __host__ __device__ int rows(const ColmapLossArgs& a) { return a.K; }
+    static __host__ __device__ double* ws(const ColmapLossArgs& a) { return a.ws; }
+    static __device__ void loop(const ColmapLossArgs& a, int first, int end, double* acc) { acc[0] = colmap_loss_loop(a, first, end); }
+    static __device__ void outputs(const ColmapLossArgs& a, const double* tot) { a.out[0] = (float)colmap_total(tot[0], a.B); }
+};
 
 }  // namespace sparf
 
@@ -153,8 +99,8 @@ static const int64_t kColmapMax = (int64_t)1 << 30;
 
 int64_t sparf_colmap_workspace_bytes(int B, int64_t n, int64_t rows) {
     int64_t compact = 0, loss = 0;
-    if (B > 0 && B <= COLMAP_MAX_IMAGES && n > COLMAP_CHUNK && n <= kColmapMax) compact = (int64_t)B * colmap_chunks(n) * 2 * (int64_t)sizeof(int32_t);
-    if (rows > COLMAP_CHUNK && rows <= kColmapMax) loss = colmap_chunks(rows) * (int64_t)sizeof(double);
+    if (B > 0 && B <= COLMAP_MAX_IMAGES && n <= kColmapMax) compact = ordered_compact_workspace_bytes<ColmapItem>(n, B);
+    if (rows <= kColmapMax) loss = ordered_sum_workspace_bytes<ColmapLossSum>(rows);
     return compact > loss ? compact : loss;
 }
 
@@ -165,15 +111,8 @@ int sparf_colmap_compact(const float* depth, int B, int H, int W, int32_t* index
     if (n == 0) return hipMemsetAsync(count, 0, 2 * (size_t)B * sizeof(int32_t), s) == hipSuccess ? 0 : 2;      // (an empty tensor has no address)
     if (!depth || !index) return 1;
     ColmapCompactArgs a{};
-    a.depth = depth; a.B = B; a.n = n; a.chunks = (int)colmap_chunks(n); a.index = index; a.count = count; a.ws = (int32_t*)workspace;
-    if (n <= COLMAP_CHUNK || !a.ws) {
-        hipLaunchKernelGGL(colmap_compact_single_kernel, dim3(1, B), dim3(COLMAP_BLOCK), 0, s, a);
-        return hipGetLastError() == hipSuccess ? 0 : 2;
-    }
-    hipLaunchKernelGGL(colmap_compact_counts_kernel, dim3(a.chunks, B), dim3(COLMAP_BLOCK), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return 2;
-    hipLaunchKernelGGL(colmap_compact_write_kernel, dim3(a.chunks, B), dim3(COLMAP_BLOCK), 0, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    a.depth = depth; a.B = B; a.n = n; a.index = index; a.count = count; a.ws = (int32_t*)workspace;
+    return launch_ordered_compact<ColmapItem>(a, B, s);
 }
 
 int sparf_colmap_gather(const int32_t* index, const int32_t* count, const int64_t* sel, int B, int H, int W, int quota, int K, const float* depth,
@@ -187,7 +126,7 @@ int sparf_colmap_gather(const int32_t* index, const int32_t* count, const int64_
     a.depth = depth; a.conf = conf; a.ray_idx = ray_idx; a.target = target; a.weight = weight;
     const int per_image = quota < a.n ? quota : a.n;
     hipLaunchKernelGGL(colmap_gather_kernel, dim3((per_image + COLMAP_BLOCK - 1) / COLMAP_BLOCK, B), dim3(COLMAP_BLOCK), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return launched();
 }
 
 int sparf_colmap_loss(const float* target, const float* weight, const int32_t* count, int B, int quota, int K, const float* depth,
@@ -195,17 +134,8 @@ int sparf_colmap_loss(const float* target, const float* weight, const int32_t* c
     if (B <= 0 || B > COLMAP_MAX_IMAGES || quota < 0 || K < 0 || (int64_t)K > kColmapMax || (d_depth_fine && !depth_fine)) return 1;
     if (K == 0) return 0;                                // nothing to launch, no pointer looked at: the loss of no rows is the caller's zero
     if (!target || !weight || !count || !depth || !out) return 1;
-    hipStream_t s = (hipStream_t)stream;
     ColmapLossArgs a{};
     a.target = target; a.weight = weight; a.count = count; a.B = B; a.quota = quota; a.K = K; a.depth = depth; a.depth_fine = depth_fine;
     a.out = out; a.d_depth = d_depth; a.d_depth_fine = d_depth_fine; a.ws = (double*)workspace;
-    if (K <= COLMAP_CHUNK || !a.ws) {
-        hipLaunchKernelGGL(colmap_loss_single_kernel, dim3(1), dim3(COLMAP_BLOCK), 0, s, a);
-        return hipGetLastError() == hipSuccess ? 0 : 2;
-    }
-    const int chunks = (int)colmap_chunks(K);
-    hipLaunchKernelGGL(colmap_loss_partial_kernel, dim3(chunks), dim3(COLMAP_BLOCK), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return 2;
-    hipLaunchKernelGGL(colmap_loss_finish_kernel, dim3(1), dim3(1), 0, s, a, chunks);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return launch_ordered_sum<ColmapLossSum>(a, (hipStream_t)stream);
 }

@@ -7,10 +7,10 @@
 // p = ray_idx[r], ray_idx[b][r] or r; no indexed copy of a map exists, and the fine head shares the coarse head's reads.  Indices may
 // repeat; nothing is scattered, so there is no atomic.  An index outside its range is the caller's error (torch raises on it); it is
 // clamped here so that the launch stays inside the maps.  No address depends on a value read from a map.
-// Sums are fixed-order (ordered.h: block_totals, sum_parts): a thread adds its rows in index order, then the wave, the waves and the
-// chunks in their order: the same bits from call to call.  Up to DEPTH_ERR_CHUNK rows (or without a workspace) one workgroup does all of
-// it in one launch; above, a launch of one workgroup per chunk that leaves partial totals and a second one that adds them.  No workgroup
-// waits for another, no host synchronisation, no readback.
+// Sums are fixed-order, by ordered.h's chunked sum over DepthErrSum: a thread adds its rows in index order, then the wave, the waves and
+// the chunks in their order: the same bits from call to call.  Up to DEPTH_ERR_CHUNK rows (or without a workspace) one workgroup does
+// all of it in one launch; above, a launch of one workgroup per chunk that leaves partial totals and a second one that adds them.  No
+// workgroup waits for another, no host synchronisation, no readback.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sparf_hip.h"
@@ -18,8 +18,6 @@
 #include "ordered.h"
 
 namespace sparf {
-
-static constexpr int DEPTH_ERR_WAVES = DEPTH_ERR_BLOCK / 64;
 
 // the rows first, first + DEPTH_ERR_BLOCK, ... < end into acc
 static __device__ void depth_err_loop(const DepthErrArgs& a, int first, int end, double acc[DEPTH_ERR_NACC]) {
@@ -30,34 +28,15 @@ static __device__ void depth_err_loop(const DepthErrArgs& a, int first, int end,
     for (int r = first; r < end; r += DEPTH_ERR_BLOCK) depth_err_row_into(a, s, r, acc);
 }
 
-// rows <= DEPTH_ERR_CHUNK (or no workspace): one workgroup
-__global__ void __launch_bounds__(DEPTH_ERR_BLOCK) depth_err_single_kernel(DepthErrArgs a) {
-    __shared__ double red[DEPTH_ERR_WAVES][DEPTH_ERR_NACC];
-    double acc[DEPTH_ERR_NACC], tot[DEPTH_ERR_NACC];
-    depth_err_loop(a, threadIdx.x, a.rows, acc);
-    block_totals<DEPTH_ERR_NACC, DEPTH_ERR_WAVES>(acc, red, tot);
-    if (threadIdx.x == 0) depth_err_outputs(tot, a.depth_fine != nullptr, a.out, a.count);
-}
-// rows > DEPTH_ERR_CHUNK, one workgroup per chunk: its totals at ws[chunk]
-__global__ void __launch_bounds__(DEPTH_ERR_BLOCK) depth_err_partial_kernel(DepthErrArgs a) {
-    __shared__ double red[DEPTH_ERR_WAVES][DEPTH_ERR_NACC];
-    double acc[DEPTH_ERR_NACC], tot[DEPTH_ERR_NACC];
-    const int first = (int)blockIdx.x * DEPTH_ERR_CHUNK;
-    depth_err_loop(a, first + (int)threadIdx.x, min(a.rows, first + DEPTH_ERR_CHUNK), acc);
-    block_totals<DEPTH_ERR_NACC, DEPTH_ERR_WAVES>(acc, red, tot);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < DEPTH_ERR_NACC; ++j) a.ws[(size_t)blockIdx.x * DEPTH_ERR_NACC + j] = tot[j];
-    }
-}
-// the partial totals added in chunk order
-__global__ void depth_err_finish_kernel(DepthErrArgs a, int chunks) {
-    double tot[DEPTH_ERR_NACC];
-    sum_parts<DEPTH_ERR_NACC>(a.ws, chunks, tot);
-    depth_err_outputs(tot, a.depth_fine != nullptr, a.out, a.count);
-}
-
-static inline int64_t depth_err_chunks(int64_t rows) { return (rows + DEPTH_ERR_CHUNK - 1) / DEPTH_ERR_CHUNK; }
+// the policy of ordered.h's chunked sum
+struct DepthErrSum {
+    typedef DepthErrArgs Args;
+    static constexpr int BLOCK = DEPTH_ERR_BLOCK, CHUNK = DEPTH_ERR_CHUNK, NACC = DEPTH_ERR_NACC;
+    static __host__ __device__ int rows(const DepthErrArgs& a) { return a.rows; }
+    static __host__ __device__ double* ws(const DepthErrArgs& a) { return a.ws; }
+    static __device__ void loop(const DepthErrArgs& a, int first, int end, double* acc) { depth_err_loop(a, first, end, acc); }
+    static __device__ void outputs(const DepthErrArgs& a, const double* tot) { depth_err_outputs(tot, a.depth_fine != nullptr, a.out, a.count); }
+};
 
 }  // namespace sparf
 
@@ -67,7 +46,7 @@ using namespace sparf;
 static const int64_t kDepthErrMax = (int64_t)1 << 30;
 
 int64_t sparf_ray_depth_err_workspace_bytes(int64_t rows) {
-    return rows > DEPTH_ERR_CHUNK && rows <= kDepthErrMax ? depth_err_chunks(rows) * DEPTH_ERR_NACC * (int64_t)sizeof(double) : 0;
+    return rows <= kDepthErrMax ? ordered_sum_workspace_bytes<DepthErrSum>(rows) : 0;
 }
 
 int sparf_ray_depth_err(const float* depth_gt, const unsigned char* valid, const int64_t* img_idx, const int64_t* ray_idx, int per_image,
@@ -83,14 +62,6 @@ int sparf_ray_depth_err(const float* depth_gt, const unsigned char* valid, const
     a.depth_gt = depth_gt; a.valid = valid; a.img_idx = img_idx; a.ray_idx = ray_idx; a.per_image = per_image;
     a.B_maps = B_maps; a.B = B; a.HW = HW; a.N = N; a.rows = rows; a.depth = depth; a.depth_fine = depth_fine;
     a.scale = scale; a.scale_dev = scale_dev; a.out = out; a.count = count; a.ws = (double*)workspace;
-    hipStream_t s = (hipStream_t)stream;
-    if (rows <= DEPTH_ERR_CHUNK || !a.ws) {              // (rows == 0: no input is read, the totals are zero: abs_e 0, rmse NaN, count 0)
-        hipLaunchKernelGGL(depth_err_single_kernel, dim3(1), dim3(DEPTH_ERR_BLOCK), 0, s, a);
-        return hipGetLastError() == hipSuccess ? 0 : 2;
-    }
-    const int chunks = (int)depth_err_chunks(rows);
-    hipLaunchKernelGGL(depth_err_partial_kernel, dim3(chunks), dim3(DEPTH_ERR_BLOCK), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return 2;
-    hipLaunchKernelGGL(depth_err_finish_kernel, dim3(1), dim3(1), 0, s, a, chunks);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    // (rows == 0: one launch, no input is read, the totals are zero: abs_e 0, rmse NaN, count 0)
+    return launch_ordered_sum<DepthErrSum>(a, (hipStream_t)stream);
 }

@@ -7,9 +7,9 @@
 // [0, HW) is the caller's error (torch raises on it); it is clamped here so that the launch stays inside the image.
 // Depth patches: a row sums over the P^2 partners of its own patch (read from global memory, wherever the patch lies relative to a
 // chunk of rows), so every row's patch sum and seed are its own and no patch is split between workgroups.
-// Sums are fixed-order (ordered.h: block_totals, sum_parts): a thread adds its rows in index order, then the wave, the waves and the
-// chunks in their order.  Up to PHOTO_CHUNK rows (or without a workspace) one workgroup does all of it in one launch; above,
-// a launch of one workgroup per chunk that leaves partial totals and a second one that adds them.  No host synchronisation, no readback.
+// Sums are fixed-order, by ordered.h's chunked sum over PhotoSum: a thread adds its rows in index order, then the wave, the waves and
+// the chunks in their order.  Up to PHOTO_CHUNK rows (or without a workspace) one workgroup does all of it in one launch; above, a
+// launch of one workgroup per chunk that leaves partial totals and a second one that adds them.  No host synchronisation, no readback.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sparf_hip.h"
@@ -17,8 +17,6 @@
 #include "photo.h"
 
 namespace sparf {
-
-static constexpr int PHOTO_WAVES = PHOTO_BLOCK / 64;
 
 struct PhotoDepths {             // the depths of one patch, by position
     const float* p;
@@ -84,46 +82,15 @@ static __device__ void photo_loop(const PhotoArgs& a, int first, int end, double
     }
 }
 
-// rows <= PHOTO_CHUNK (or no workspace): one workgroup
-__global__ void __launch_bounds__(PHOTO_BLOCK) photo_regu_single_kernel(PhotoArgs a) {
-    __shared__ double red[PHOTO_WAVES][PHOTO_NACC];
-    double acc[PHOTO_NACC], tot[PHOTO_NACC];
-    photo_loop(a, threadIdx.x, a.rows, acc);
-    block_totals<PHOTO_NACC, PHOTO_WAVES>(acc, red, tot);
-    if (threadIdx.x == 0) photo_outputs(a, tot);
-}
-// rows > PHOTO_CHUNK, one workgroup per chunk: its totals at ws[b]
-__global__ void __launch_bounds__(PHOTO_BLOCK) photo_regu_partial_kernel(PhotoArgs a) {
-    __shared__ double red[PHOTO_WAVES][PHOTO_NACC];
-    double acc[PHOTO_NACC], tot[PHOTO_NACC];
-    const int first = (int)blockIdx.x * PHOTO_CHUNK;
-    photo_loop(a, first + (int)threadIdx.x, min(a.rows, first + PHOTO_CHUNK), acc);
-    block_totals<PHOTO_NACC, PHOTO_WAVES>(acc, red, tot);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < PHOTO_NACC; ++j) a.ws[(size_t)blockIdx.x * PHOTO_NACC + j] = tot[j];
-    }
-}
-// the partial totals added in chunk order
-__global__ void photo_regu_finish_kernel(PhotoArgs a, int chunks) {
-    double tot[PHOTO_NACC];
-    sum_parts<PHOTO_NACC>(a.ws, chunks, tot);
-    photo_outputs(a, tot);
-}
-
-static inline int64_t photo_chunks(int64_t rows) { return (rows + PHOTO_CHUNK - 1) / PHOTO_CHUNK; }
-
-static int launch_photo_regu(const PhotoArgs& a, hipStream_t s) {
-    if (a.rows <= PHOTO_CHUNK || !a.ws) {
-        hipLaunchKernelGGL(photo_regu_single_kernel, dim3(1), dim3(PHOTO_BLOCK), 0, s, a);
-        return hipGetLastError() == hipSuccess ? 0 : 2;
-    }
-    const int chunks = (int)photo_chunks(a.rows);
-    hipLaunchKernelGGL(photo_regu_partial_kernel, dim3(chunks), dim3(PHOTO_BLOCK), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return 2;
-    hipLaunchKernelGGL(photo_regu_finish_kernel, dim3(1), dim3(1), 0, s, a, chunks);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-}
+// the policy of ordered.h's chunked sum
+struct PhotoSum {
+    typedef PhotoArgs Args;
+    static constexpr int BLOCK = PHOTO_BLOCK, CHUNK = PHOTO_CHUNK, NACC = PHOTO_NACC;
+    static __host__ __device__ int rows(const PhotoArgs& a) { return a.rows; }
+    static __host__ __device__ double* ws(const PhotoArgs& a) { return a.ws; }
+    static __device__ void loop(const PhotoArgs& a, int first, int end, double* acc) { photo_loop(a, first, end, acc); }
+    static __device__ void outputs(const PhotoArgs& a, const double* tot) { photo_outputs(a, tot); }
+};
 
 }  // namespace sparf
 
@@ -133,7 +100,7 @@ using namespace sparf;
 static const int64_t kPhotoMaxRows = (int64_t)1 << 30;
 
 int64_t sparf_photo_regu_workspace_bytes(int64_t rows) {
-    return rows > PHOTO_CHUNK && rows <= kPhotoMaxRows ? photo_chunks(rows) * PHOTO_NACC * (int64_t)sizeof(double) : 0;
+    return rows <= kPhotoMaxRows ? ordered_sum_workspace_bytes<PhotoSum>(rows) : 0;
 }
 
 int sparf_photo_regu_loss(const float* image, const unsigned char* fg_mask, const int64_t* ray_idx, int per_image, int B, int HW, int N,
@@ -158,5 +125,5 @@ int sparf_photo_regu_loss(const float* image, const unsigned char* fg_mask, cons
     a.opacity = opacity; a.opacity_fine = opacity_fine; a.depth = depth; a.depth_fine = depth_fine; a.out = out;
     a.d_rgb = d_rgb; a.d_rgb_fine = d_rgb_fine; a.d_opacity = d_opacity; a.d_opacity_fine = d_opacity_fine;
     a.d_depth = d_depth; a.d_depth_fine = d_depth_fine; a.ws = (double*)workspace;
-    return launch_photo_regu(a, s);
+    return launch_ordered_sum<PhotoSum>(a, s);
 }

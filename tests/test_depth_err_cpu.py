@@ -361,4 +361,7 @@ def test_the_unit_takes_its_block_sums_from_ordered_h():
     assert '#include "ordered.h"' in text and '#include "depth_err.h"' in text
     for word in ("__ballot", "__shfl_xor", "atomicAdd", "asm"):
         assert word not in text, f"depth_err.hip has a {word} of its own"
-    assert "block_totals<DEPTH_ERR_NACC" in text and "sum_parts<DEPTH_ERR_NACC>" in text
+    # the sums are ordered.h's chunked sum over the unit's policy, which hands it DEPTH_ERR_NACC totals
+    assert "launch_ordered_sum<DepthErrSum>" in text and "NACC = DEPTH_ERR_NACC" in text
+    header = open(os.path.join(BUILD.CSRC, "ordered.h")).read()
+    assert "block_totals<S::NACC" in header and "sum_parts<S::NACC>" in header

@@ -55,6 +55,41 @@ def test_kernel_stream_diff_compares_listings_without_addresses_and_comments():
     assert d["lines"] == (7, 7) and d["hist"] == {"ds_read_b128": [1, 0], "ds_read_b64": [0, 1]} and d["only"] == (1, 1) and d["in_tile_loop"] == (1, 1)
 
 
+def test_kernel_stream_diff_pairs_renamed_kernels_and_ignores_the_padding_behind_a_kernel():
+    """A refactor that turns kernels into template instances renames them: with a table of `old name = new name` lines the diff
+    compares each under its new name; without it they are ONLY_A and ONLY_B.  The s_nop padding behind the last kernel of a section
+    belongs to no kernel's code; whatever else follows a kernel's last s_endpgm does."""
+    m = _load("tools/kernel_stream.py", "kernel_stream_renames")
+    body = ["\ts_load_dword s0, s[0:1], 0x0   // 000000001000:", "\tv_add_f64 v[0:1], v[0:1], v[2:3]   // 000000001008:", "\ts_endpgm   // 000000001010:"]
+    pad = ["\ts_nop 0   // 000000001014:", "\ts_nop 0   // 000000001018:"]
+    other = body[:1] + ["\tv_mul_f64 v[0:1], v[0:1], v[2:3]   // 000000001008:"] + body[2:]
+    a = {"sparf::unit_single_kernel": body + pad, "sparf::unit_finish_kernel": body, "sparf::unit_gather_kernel": body}
+    b = {"sparf::sum_single_kernel<sparf::Unit>": body, "sparf::sum_finish_kernel<sparf::Unit>": other, "sparf::unit_gather_kernel": body + pad}
+    verdicts = lambda a, b: {name: verdict for name, verdict, _ in m.compare_listings(a, b)}
+    assert verdicts(a, b) == {"sparf::unit_single_kernel": "ONLY_A", "sparf::unit_finish_kernel": "ONLY_A", "sparf::unit_gather_kernel": "IDENTICAL",
+                              "sparf::sum_single_kernel<sparf::Unit>": "ONLY_B", "sparf::sum_finish_kernel<sparf::Unit>": "ONLY_B"}
+    table = m.read_renames("# the two kernels of the sum\n\nsparf::unit_single_kernel = sparf::sum_single_kernel<sparf::Unit>\n"
+                           "sparf::unit_finish_kernel = sparf::sum_finish_kernel<sparf::Unit>\n")
+    assert table == {"sparf::unit_single_kernel": "sparf::sum_single_kernel<sparf::Unit>", "sparf::unit_finish_kernel": "sparf::sum_finish_kernel<sparf::Unit>"}
+    names = m.renamed({k: k for k in a}, table)
+    assert verdicts({names[k]: v for k, v in a.items()}, b) == {"sparf::sum_single_kernel<sparf::Unit>": "IDENTICAL",
+                                                                "sparf::sum_finish_kernel<sparf::Unit>": "DIFFER", "sparf::unit_gather_kernel": "IDENTICAL"}
+    try:
+        m.read_renames("sparf::unit_single_kernel sparf::sum_single_kernel")
+    except ValueError:
+        pass
+    else:
+        raise AssertionError("a line without ` = ` was accepted")
+    # only that padding is dropped: a block the compiler laid out behind the last s_endpgm is the kernel's code and is compared
+    tail = ["\tv_mov_b32 v0, 0   // 000000001014:", "\ts_branch 65530   // 000000001018:"]
+    moved = [tail[0].replace("v0, 0", "v0, 1"), tail[1]]
+    assert verdicts({"k": body + tail + pad}, {"k": body + tail}) == {"k": "IDENTICAL"}
+    assert verdicts({"k": body + tail}, {"k": body + moved + pad}) == {"k": "DIFFER"}
+    assert verdicts({"k": body + tail}, {"k": body}) == {"k": "DIFFER"}
+    (_, _, d), = m.compare_listings({"k": body + tail + pad}, {"k": body + tail})
+    assert d["lines"] == (5, 5)
+
+
 def test_fp8_emulation_matches_torch_casts():
     """tests/tools/save_precision_study.py rounds with its own arithmetic (a per-tile scale, then the 8-bit grid): with the scale
     forced to one the grid must be torch's float8_e4m3fn / float8_e5m2 (round to nearest even, subnormals, saturation)."""
@@ -89,17 +124,27 @@ def test_emulated_linear_is_the_plain_one_without_rounding():
 
 def test_loss_units_take_ordered_compaction_and_block_sums_from_ordered_h():
     """The loss kernels' two promises -- a selection in torch.where's order bit for bit, sums with the same bits from call to call --
-    rest on the wave ballot ranks and the fixed-order block sums of csrc/ordered.h.  The five units call that one copy: each includes
-    the header and holds no ballot and no shuffle butterfly of its own, comments included (a sixth loss unit belongs in the list)."""
+    rest on the wave ballot ranks and the fixed-order block sums of csrc/ordered.h.  The six units call that one copy: each includes
+    the header and holds no ballot and no shuffle butterfly of its own, comments included (a seventh loss unit belongs in the list).
+    The chunked launch schemes around those routines -- single / partial / finish kernels of a sum, single / counts / write kernels of
+    a compaction -- are ordered.h's templates too: no unit defines such a kernel of its own, but reproj.hip, whose strided grid with a
+    seeds pass is another scheme."""
+    import re
     from sparf_amd import build as B
     assert "ordered.h" in B.HEADERS, "source_hash() does not cover ordered.h"
     header = open(os.path.join(B.CSRC, "ordered.h")).read()
     assert "__ballot" in header and "__shfl_xor" in header
-    for unit in ("reproj.hip", "dcons.hip", "photo.hip", "matches.hip", "colmap.hip"):
+    scheme = re.compile(r"__global__\s+void\s+(?:__launch_bounds__\([^)]*\)\s*)?(\w+_(?:single|partial|finish|counts|write)_kernel)\s*\(")
+    assert {"ordered_sum_single_kernel", "ordered_sum_partial_kernel", "ordered_sum_finish_kernel", "ordered_compact_single_kernel",
+            "ordered_compact_counts_kernel", "ordered_compact_write_kernel"} <= set(scheme.findall(header))
+    for unit in ("reproj.hip", "dcons.hip", "photo.hip", "matches.hip", "colmap.hip", "depth_err.hip"):
         text = open(os.path.join(B.CSRC, unit)).read()
         assert '#include "ordered.h"' in text, f"{unit} does not include ordered.h"
         for word in ("__ballot", "__shfl_xor"):
             assert word not in text, f"{unit} has a {word} of its own: the routine lives in ordered.h"
+        if unit != "reproj.hip":
+            assert not scheme.findall(text), f"{unit} defines {scheme.findall(text)}: the chunked launch schemes live in ordered.h"
+    assert scheme.findall(open(os.path.join(B.CSRC, "reproj.hip")).read()) == ["reproj_single_kernel", "reproj_partial_kernel"]      # (the pattern finds them)
 
 
 def test_shipped_kernels_have_no_experiment_or_probe_flag_on():

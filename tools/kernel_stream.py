@@ -2,9 +2,12 @@
 
     python tools/kernel_stream.py [translation unit ...]        (default: the two config-1 units of the bf16x3 mode; `all` = every
                                                                  fused MLP kernel unit but the ray-gradient-only ones)
-    python tools/kernel_stream.py diff <object dir A> <object dir B>     (every kernel of every unit both directories hold: IDENTICAL, or
-                                                                 DIFFER with what differs; e.g. sparf_amd/csrc_<tag> of tools/build_variant.py
-                                                                 against sparf_amd/csrc/build -- a refactor's proof of "same machine code")
+    python tools/kernel_stream.py diff <object dir A> <object dir B> [renames]   (every kernel of every unit both directories hold:
+                                                                 IDENTICAL, or DIFFER with what differs; e.g. sparf_amd/csrc_<tag> of
+                                                                 tools/build_variant.py against sparf_amd/csrc/build -- a refactor's proof
+                                                                 of "same machine code".  renames: a file of `name in A = name in B` lines
+                                                                 for kernels the refactor renamed, which are then compared under B's name
+                                                                 instead of being listed as ONLY_A and ONLY_B)
 
 Reads the gfx950 code object out of sparf_amd/csrc/build/<unit>.o (compiles the unit into a scratch directory when there is no
 object newer than its sources) and prints, per kernel: MFMAs, all other instructions, s_nop, v_readlane_b32 / v_writelane_b32
@@ -114,6 +117,15 @@ def parsed(lines):
     return out
 
 
+def code_of(listing):
+    """a parsed listing without the s_nop lines at its end: the padding behind the last kernel of a section, which moves to another
+    kernel when a refactor reorders them.  Everything else stays, blocks laid out behind the last s_endpgm included."""
+    end = len(listing)
+    while end and listing[end - 1][0].split()[0] == "s_nop":
+        end -= 1
+    return listing[:end]
+
+
 def mfma_loops(listing):
     """address ranges [target, branch] of the backward branches that enclose an MFMA: the tile loops"""
     mf = [a for t, a in listing if t.startswith("v_mfma") and a is not None]
@@ -138,7 +150,7 @@ def compare_listings(a, b):
         if name not in a or name not in b:
             out.append((name, "ONLY_A" if name in a else "ONLY_B", None))
             continue
-        pa, pb = parsed(a[name]), parsed(b[name])
+        pa, pb = code_of(parsed(a[name])), code_of(parsed(b[name]))
         if [t for t, _ in pa] == [t for t, _ in pb]:
             out.append((name, "IDENTICAL", {"lines": (len(pa), len(pb))}))
             continue
@@ -196,8 +208,27 @@ def kernel_names(mangled):
     return out
 
 
-def diff_dirs(dir_a, dir_b):
-    """print the comparison of every unit (object file name) the two object directories share"""
+def read_renames(text):
+    """{name in A: name in B} from lines `old name = new name` (demangled, without return type and argument list, as the diff prints
+    them); empty lines and lines that start with # are skipped"""
+    out = {}
+    for line in text.split("\n"):
+        if line.strip() and not line.lstrip().startswith("#"):
+            old, sep, new = line.partition(" = ")
+            if not sep or not old.strip() or not new.strip():
+                raise ValueError(f"not an `old name = new name` line: {line!r}")
+            out[old.strip()] = new.strip()
+    return out
+
+
+def renamed(names, renames):
+    """{key: kernel name} of side A with the renamed kernels under their names in B"""
+    return {k: renames.get(name, name) for k, name in names.items()}
+
+
+def diff_dirs(dir_a, dir_b, renames=None):
+    """print the comparison of every unit (object file name) the two object directories share; renames: {kernel name in A: in B}"""
+    renames = renames or {}
     units = lambda d: {f for f in os.listdir(d) if f.endswith(".o")}
     ua, ub = units(dir_a), units(dir_b)
     for f in sorted(ua ^ ub):
@@ -212,6 +243,7 @@ def diff_dirs(dir_a, dir_b):
             # (kernels only -- the names the notes list; not device functions or labels)
             by_name = lambda d, names: {names[k]: v for k, v in d.items() if k in names}
             ka, kb = kernel_names(notes_of(ca)), kernel_names(notes_of(cb))
+            ka = renamed(ka, renames)
             na, nb = by_name(notes_of(ca), ka), by_name(notes_of(cb), kb)
             sa, sb = by_name(streams_of(ca), ka), by_name(streams_of(cb), kb)
             for name, verdict, d in compare_listings(by_name(listings_of(ca), ka), by_name(listings_of(cb), kb)):
@@ -227,7 +259,7 @@ def diff_dirs(dir_a, dir_b):
 
 if __name__ == "__main__":
     if sys.argv[1:2] == ["diff"]:
-        diff_dirs(sys.argv[2], sys.argv[3])
+        diff_dirs(sys.argv[2], sys.argv[3], read_renames(open(sys.argv[4]).read()) if sys.argv[4:] else None)
         sys.exit(0)
     for unit in MLP_UNITS if sys.argv[1:] == ["all"] else sys.argv[1:] or ["mlp_fwd_x3_train.hip", "mlp_bwd_x3.hip"]:
         for name, f in figures(unit).items():

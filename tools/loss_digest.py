@@ -1,5 +1,5 @@
-"""SHA-256 digests of every output tensor of the five loss units that share csrc/ordered.h (reproj, dcons, photo, matches, colmap), at
-the sizes either side of each unit's one-launch limit, for the seeded inputs of the referee modules in tests/ -- run it under two
+"""SHA-256 digests of every output tensor of the six loss units that share csrc/ordered.h (reproj, dcons, photo, matches, colmap,
+depth_err), at the sizes either side of each unit's one-launch limit, for the seeded inputs of the referee modules in tests/ -- run it under two
 $SPARF_LIB builds to show that a change to the ordered compaction or the fixed-order sums is bit-neutral.
 
     python tools/loss_digest.py ;  SPARF_LIB=sparf_amd/libsparf_hip_base.so python tools/loss_digest.py
@@ -14,8 +14,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "compat")]
 from sparf_amd import losses, ops                                                    # noqa: E402
-from tests import colmap_referee, dcons_referee, matches_referee, photo_referee, reproj_referee                      # noqa: E402
-from tests import test_colmap_gpu, test_dcons_gpu, test_matches_gpu, test_photo_gpu, test_reproj_gpu                 # noqa: E402
+from tests import colmap_referee, dcons_referee, depth_err_referee, matches_referee, photo_referee, reproj_referee   # noqa: E402
+from tests import test_colmap_gpu, test_dcons_gpu, test_depth_err_gpu, test_matches_gpu, test_photo_gpu, test_reproj_gpu      # noqa: E402
 
 
 def digest(t):
@@ -90,8 +90,18 @@ def colmap():
     line("colmap", "loss_fine", "+".join(map(str, rows)), [("loss", loss)] + [(f"seed{i}", x) for i, x in enumerate(grads)])
 
 
+def depth_err():
+    R, T = depth_err_referee, test_depth_err_gpu
+    cases = [("per_image", R.build("per_image"))] + [("x".join(map(str, shape)), R.build_edge(*shape)) for shape in R.EDGE_SHAPES]      # 4096, 4097, 8710 rows
+    for size, case in cases:
+        for scale in R.SCALES:
+            for fine in (True, False):
+                vector, count, _ = T.run(case, scale, fine)
+                line("depth_err", "fine" if fine else "coarse", f"{size}_s{scale}", [("vector", vector), ("count", count)])
+
+
 if __name__ == "__main__":
     print("library:", os.environ.get("SPARF_LIB", "default"), flush=True)
-    for unit in (reproj, dcons, photo, matches, colmap):
+    for unit in (reproj, dcons, photo, matches, colmap, depth_err):
         unit()
     torch.cuda.synchronize()
