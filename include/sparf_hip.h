@@ -438,6 +438,38 @@ int sparf_ray_depth_err(const float* depth_gt, const unsigned char* valid /*NULL
                         const float* depth, const float* depth_fine /*NULL ok*/, float scale, const float* scale_dev /*NULL ok*/,
                         float* out, int32_t* count, void* workspace /*NULL ok*/, void* stream);
 
+/* ---- depth-consistency front end and ray sampler ------------------------------
+ * sparf_pick_pixels: the pixels of sample_rays / sample_rays_for_patch / RaySamplingStrategy.__call__
+ * (source/training/core/sampling_strategies.py:132-296) from permutation prefixes already on the
+ * device, ONE launch, one thread per output row.
+ * perm_a [n_a], perm_b [n_b] (int64, device; NULL with a count of 0) index two rectangular pools
+ *   given by value: pool A is the grid [0,a_w) x [0,a_h), index i -> (i % a_w, i / a_w); pool B is
+ *   the box of b_w x b_h pixels at (b_x0, b_y0), row-major (the reference's linspace centre box).
+ *   An entry outside [0, pool size) is the caller's error; it is clamped into the pool.
+ * Rows: the picks of A, then the picks of B, each expanded by the patch x patch offsets (dy outer,
+ *   dx inner): (n_a + n_b) patch^2 rows.  pixels [rows][2] float32 (x, y) and / or rays [rows] int64
+ *   = y W + x; either may be NULL (both NULL, or no row: nothing is launched, returns 0).
+ * Returns 1 before any HIP call for a negative count, W <= 0, patch outside [1, 1024], more than
+ * 2^30 rows, or a pool with picks that has no permutation, a negative origin, no pixel, more than
+ * 2^30 pixels, or whose origin + width + patch - 1 exceeds W.
+ *
+ * sparf_unseen_pose: DepthConsistencyLoss.sample_pose (depth_cons_loss.py:45-63) with the pose
+ * preparation in front of it (:103-106, :168-174), ONE launch of one wave.
+ * poses_w2c [B][row_floats] float32, row_floats 12 ([B,3,4]) or 16 ([B,4,4]).
+ * Camera centres -R^T t in float32; angular distances acos(clip(u_self . u_j, -1, 1)),
+ *   u = v / (|v| + 1e-6), in double on the float32 centres; the self entry is 1e3; id_other = the
+ *   first index of the minimum (B == 1: 0).
+ * pose_w2c_ref = poses_w2c[id_self] as a 4 x 4, pose_c2w_ref its transpose inverse, pose_c2w_other
+ *   the transpose inverse of poses_w2c[id_other], pose_w2c_at_unseen the transpose inverse of
+ *   w c2w_ref + one_minus_w c2w_other (element-wise: two rounded products, one rounded sum).
+ * Returns 1 before any HIP call for row_floats outside {12, 16}, B < 1 or above 2^20, id_self
+ * outside [0, B) or a missing pointer. */
+int sparf_pick_pixels(const int64_t* perm_a /*NULL ok*/, int n_a, const int64_t* perm_b /*NULL ok*/, int n_b, int a_w, int a_h,
+                      int b_x0, int b_y0, int b_w, int b_h, int W, int patch, float* pixels /*NULL ok*/, int64_t* rays /*NULL ok*/,
+                      void* stream);
+int sparf_unseen_pose(const float* poses_w2c, int row_floats, int B, int id_self, float w, float one_minus_w, float* pose_w2c_ref,
+                      float* pose_c2w_ref, float* pose_c2w_other, float* pose_w2c_at_unseen, int32_t* id_other, void* stream);
+
 /* ---- evaluation metrics ----------------------------------------------------
  * compute_metrics / compute_metrics_masked / compute_depth_error (source/training/core/metrics.py:
  * 136-268, called per head by source/training/base.py:475-499 and nerf_trainer.py:387-405) with the

@@ -16,8 +16,8 @@ FUSED_UNITS = ["mlp_fwd_fp32_train.hip", "mlp_fwd_fp32_infer.hip", "rays_fwd_fp3
                "mlp_fwd_bf16_train.hip", "mlp_fwd_bf16_train_q8.hip", "mlp_fwd_bf16_infer.hip"]
 RAYS_UNITS = ["rays_fwd_fp32.hip", "rays_bwd_fp32.hip", "rays_fwd_x3.hip", "rays_bwd_x3.hip", "rays_bwd_x3w4.hip", "rays_bwd.hip", "rays_fwd_bf16.hip"]
 MLP_DISPATCH = "mlp_launch.hip"      # their dispatch: host code only
-SOURCES = FUSED_UNITS + ["wgrad.hip", "api.hip", MLP_DISPATCH, "ray_ops.hip", "pose.hip", "pose_eval.hip", "reproj.hip", "dcons.hip", "photo.hip", "matches.hip", "colmap.hip", "depth_err.hip", "metrics.hip", "pack.hip", "optim.hip", "calib.hip", "tables.cpp"]
-HEADERS = ["layout.h", "streams.h", "mlp_dev.h", "mlp_fwd_impl.h", "mlp_bwd_impl.h", "kernels.h", "pass_plan.h", "ordered.h", "reproj.h", "dcons.h", "photo.h", "matches.h", "colmap.h", "depth_err.h", "metrics.h", "pose_eval.h", "rigid.h", os.path.join("..", "..", "include", "sparf_hip.h")]
+SOURCES = FUSED_UNITS + ["wgrad.hip", "api.hip", MLP_DISPATCH, "ray_ops.hip", "pose.hip", "pose_eval.hip", "reproj.hip", "dcons.hip", "photo.hip", "matches.hip", "colmap.hip", "depth_err.hip", "pick.hip", "metrics.hip", "pack.hip", "optim.hip", "calib.hip", "tables.cpp"]
+HEADERS = ["layout.h", "streams.h", "mlp_dev.h", "mlp_fwd_impl.h", "mlp_bwd_impl.h", "kernels.h", "pass_plan.h", "ordered.h", "reproj.h", "dcons.h", "photo.h", "matches.h", "colmap.h", "depth_err.h", "pick.h", "metrics.h", "pose_eval.h", "rigid.h", os.path.join("..", "..", "include", "sparf_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-fconstexpr-steps=200000000"]
 
 

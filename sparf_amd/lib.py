@@ -143,6 +143,8 @@ EXPORTS = {
     "sparf_colmap_loss": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 7),
     "sparf_ray_depth_err_workspace_bytes": (c_int64, [c_int64]),
     "sparf_ray_depth_err": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 2 + [c_float] + [c_void_p] * 5),
+    "sparf_pick_pixels": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_int] * 8 + [c_void_p] * 3),
+    "sparf_unseen_pose": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float] + [c_void_p] * 6),
     "sparf_image_metrics_workspace_bytes":(c_int64, [c_int, c_int, c_int]),
     "sparf_image_metrics": (c_int, [POINTER(ImageMetrics), c_void_p]),
     "sparf_pose_eval": (c_int, [POINTER(PoseEval), c_void_p]),

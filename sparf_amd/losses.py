@@ -1,5 +1,6 @@
 """The correspondence loss and, below it, the depth-consistency loss, the photometric, mask and
-depth-patch loss, the correspondence sampler and the DS-NeRF sparse depth loss.
+depth-patch loss, the correspondence sampler, the DS-NeRF sparse depth loss
+and the depth-consistency front end and ray sampler.
 
 The correspondence loss: SPARF's re-projection of rendered depth at matched pixels through the current relative
 pose (corres_loss.py:50-95, :183-219; batched_geometry_utils.py:199-228; base_losses.py:197-224).
@@ -29,10 +30,17 @@ The DS-NeRF sparse depth loss (base_losses.py:326-402) is `sp
 valid pixels of every COLMAP map (ops.colmap_compact), one readback of the 2 B counts, torch.randperm as the reference calls it, a
 gather of the selected rows (ops.colmap_gather) -- and `sparse_depth_loss` (ops.ColmapLoss: the value and both seeds in one call);
 `install_colmap_depth()` puts a method under the reference's name that issues every render before it reads any.
+
+The depth-consistency front end and the ray sampler (SURVEY 8f next-14; depth_cons_loss.py:45-63, :103-106, :168-188;
+sampling_strategies.py:132-296) are `sample_pixels` (ops.pick_pixels: one launch behind one copy of the drawn permutation prefix) and
+`sample_unseen_pose` (ops.unseen_pose: the nearest other camera, the blend and the inverses in one launch, no readback), each with a
+torch restatement; `install_depth_consistency_sampler()` and `install_ray_sampler()` put the methods that hold those lines under the
+reference's names.  The random draws stay the reference's.
 """
 import collections
 import contextlib
 
+import numpy as np
 import torch
 
 from . import ops
@@ -1026,3 +1034,296 @@ def install_colmap_depth(base_losses_module):
 
 def uninstall_colmap_depth():
     _colmap.restore()
+
+
+# ================================================================================================ the depth-consistency front end and the ray sampler
+# what runs in front of the renders.  DepthConsistencyLoss.sample_pose (depth_cons_loss.py:45-63: a readback of every
+# pose, get_nearest_pose_ids in numpy, a blend and two pose_inverse_4x4 chains), the pose preparation of compute_loss and
+# compute_loss_from_existing_pixels (:103-106, :168-174: a [0,0,0,1] row from numpy, repeat, cat, a batched inverse) and sample_rays
+# (sampling_strategies.py:250-296: a host meshgrid of the whole image and a synchronous copy) become `sample_unseen_pose` (ops.unseen_pose,
+# one launch) and `sample_pixels` (ops.pick_pixels, one launch behind one copy of the drawn permutation prefix);
+# RaySamplingStrategy.__call__ (:132-188) takes the same kernel.  The random draws stay the reference's, on the generators and in the order
+# and amounts it uses: they are the parity contract with an unmodified trainer.  The in-mask pool (cv2.dilate in the constructor) is not
+# part of it: a config with sample_fraction_in_fg_mask > 0 is handed to the original method.
+def _on_gpu(device):
+    """the device test of the routes below (the tests' stand-in for the library replaces it)"""
+    return device.type == "cuda"
+
+
+def _centre_box(H, W, precrop_frac):
+    """sampling_strategies.py:105-115, :265-271: the linspace centre box as (x0, y0, width, height); its values are exact integers"""
+    dH, dW = int(H // 2 * precrop_frac), int(W // 2 * precrop_frac)
+    return W // 2 - dW, H // 2 - dH, 2 * dW, 2 * dH
+
+
+def _pick_counts(nbr, fraction_in_center):
+    """(picks of the whole pool, picks of the centre box) of sample_rays / sample_rays_for_patch"""
+    n_center = int(nbr * fraction_in_center) if fraction_in_center > 0. else 0
+    return nbr - n_center, n_center
+
+
+def _patched_torch(x_ind, y_ind, patch):
+    """sampling_strategies.py:198-201, :240-243: every pick expanded by the patch offsets, dy outer, dx inner -> [n, patch^2, 2]"""
+    r = torch.arange(patch, dtype=torch.long, device=x_ind.device)
+    Y, X = torch.meshgrid(r, r, indexing="ij")
+    x_ind = (x_ind[:, None].repeat(1, patch ** 2) + X.reshape(-1)).reshape(-1)
+    y_ind = (y_ind[:, None].repeat(1, patch ** 2) + Y.reshape(-1)).reshape(-1)
+    return torch.stack([x_ind, y_ind], dim=-1).reshape(-1, patch ** 2, 2)
+
+
+def sample_pixels_torch(H, W, nbr=None, *, precrop_frac=0.5, fraction_in_center=0., patch_size=None, perm=None, perm_center=None, device=None):
+    """sampling_strategies.py:250-296 sample_rays (patch_size None: -> pixels [n,2], rays [n]) and :191-247 sample_rays_for_patch
+    (-> [n, patch^2, 2], [n, patch^2]) in the reference's operations: the pool of (H - 1)(W - 1) pixels, or (H - (patch - 1))(W - (patch
+    - 1)); with a centre fraction int(nbr fraction) picks of the centre box behind nbr - that many of the pool; with nbr None nothing is
+    drawn and the whole pool comes back, centre fraction or not.  perm / perm_center: the drawn prefixes (None: torch.randperm on the
+    CPU generator, sliced, the pool's first).  pixels float32; rays int64 (the reference leaves float32 rays behind a centre fraction,
+    the same integers)."""
+    dev = ops._resolve(device if device is not None else perm.device if perm is not None else "cpu")
+    border = 1 if patch_size is None else patch_size - 1
+    Y, X = torch.meshgrid(torch.arange(H - border, dtype=torch.long), torch.arange(W - border, dtype=torch.long), indexing="ij")
+    x_ind, y_ind = X.reshape(-1).to(dev), Y.reshape(-1).to(dev)
+    if nbr is not None:
+        n_all, n_center = _pick_counts(nbr, fraction_in_center)
+        if perm is None:
+            perm = torch.randperm(len(x_ind))[:n_all]
+        perm = perm.to(dev)
+        x_ind, y_ind = x_ind[perm], y_ind[perm]
+        if fraction_in_center > 0.:
+            x0, y0, bw, bh = _centre_box(H, W, precrop_frac)
+            Yc, Xc = torch.meshgrid(torch.linspace(y0, y0 + bh - 1, bh), torch.linspace(x0, x0 + bw - 1, bw), indexing="ij")
+            centre = torch.stack([Xc, Yc], -1).view(-1, 2)
+            if perm_center is None:
+                perm_center = torch.randperm(len(centre))[:n_center]
+            centre = centre.to(dev)[perm_center.to(dev)].long()
+            x_ind, y_ind = torch.cat((x_ind, centre[..., 0])), torch.cat((y_ind, centre[..., 1]))
+    if patch_size is None:
+        coords = torch.stack([x_ind, y_ind], dim=-1).reshape(len(x_ind), -1)
+    else:
+        coords = _patched_torch(x_ind, y_ind, patch_size)
+    return coords.float(), coords[..., 1] * W + coords[..., 0]
+
+
+def sample_pixels(H, W, nbr=None, *, precrop_frac=0.5, fraction_in_center=0., patch_size=None, perm=None, perm_center=None, device=None):
+    """The pixels of sample_rays (patch_size None) / sample_rays_for_patch as `sample_pixels_torch` describes them, on `device`:
+    -> (pixels float32, rays int64).  The permutations are drawn as the reference draws them -- torch.randperm of the pool on the CPU
+    generator, the pool's before the centre box's, sliced -- and only the prefixes go to the device, in one non-blocking copy; one launch
+    (ops.pick_pixels) writes both results.  Prefixes already on the device are used where they are.  CPU, nbr None and a centre box whose
+    patches leave the image take the restatement."""
+    H, W = int(H), int(W)
+    dev = ops._resolve(device if device is not None else perm.device if perm is not None else "cpu")
+    patch = 1 if patch_size is None else int(patch_size)
+    border = 1 if patch_size is None else patch - 1
+    a_w, a_h = W - border, H - border
+    box = _centre_box(H, W, precrop_frac) if fraction_in_center > 0. else None
+    takes = (not _unfused and _on_gpu(dev) and nbr is not None and patch >= 1 and a_w > 0 and a_h > 0 and
+             all(t is None or (t.dtype == torch.int64 and t.dim() == 1) for t in (perm, perm_center)) and
+             (box is None or (box[0] >= 0 and box[1] >= 0 and box[2] > 0 and box[3] > 0 and box[0] + box[2] + patch - 1 <= W)))
+    if not takes:
+        return sample_pixels_torch(H, W, nbr, precrop_frac=precrop_frac, fraction_in_center=fraction_in_center, patch_size=patch_size, perm=perm,
+                                   perm_center=perm_center, device=dev)
+    n_all, n_center = _pick_counts(nbr, fraction_in_center)
+    if perm is None:
+        perm = torch.randperm(a_w * a_h)[:n_all]
+    if box is None:
+        perm_center = None
+    elif perm_center is None:
+        perm_center = torch.randperm(box[2] * box[3])[:n_center]
+    perm, perm_center = _prefixes_to(dev, perm, perm_center)
+    pixels, rays = ops.pick_pixels(perm, perm_center, (a_w, a_h), box, W, patch, device=dev)
+    if patch_size is None:
+        return pixels, rays
+    return pixels.reshape(-1, patch ** 2, 2), rays.reshape(-1, patch ** 2)
+
+
+def _prefixes_to(dev, perm, perm_center):
+    """both prefixes on `dev` (resolved: with its index): the ones elsewhere travel together, as one non-blocking copy"""
+    there = lambda t: ops._resolve(t.device) == dev
+    host = [t for t in (perm, perm_center) if t is not None and not there(t)]
+    if not host:
+        return perm, perm_center
+    both = (host[0] if len(host) == 1 else torch.cat(host)).to(dev, non_blocking=True)
+    parts = list(both.split([t.numel() for t in host]))
+    take = lambda t: t if t is None or there(t) else parts.pop(0)
+    return take(perm), take(perm_center)
+
+
+def _pose_inverse_batched_torch(mat):
+    """camera.py:44-55, the transpose form on [B,4,4]"""
+    out = torch.zeros_like(mat)
+    out[:, 3, 3] = 1
+    R_inv = mat[:, :3, :3].transpose(-1, -2)
+    out[:, :3] = torch.cat([R_inv, (-R_inv @ mat[:, :3, 3:])[..., 0][..., None]], dim=-1)
+    return out
+
+
+def nearest_other_pose_torch(centres, id_self):
+    """get_nearest_pose_ids (data_utils.py:248-311) with one neighbour, 'vector' and the scene centre 0, in float64 on the float32 camera
+    centres [B,3] as numpy computes it; the self entry is 1e3.  -> the first index of the minimum, a 0-dim int32 tensor: no readback"""
+    v = centres.double()
+    unit = v / (((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]).sqrt()[:, None] + 1e-6)
+    p = unit[id_self][None] * unit
+    dists = torch.acos(torch.clamp((p[:, 0] + p[:, 1]) + p[:, 2], -1.0, 1.0))
+    dists[id_self] = 1e3
+    index = torch.arange(len(dists), device=dists.device)
+    return torch.where(dists == dists.min(), index, len(dists)).min().to(torch.int32)
+
+
+def _blend_and_invert_torch(pose_c2w_self, pose_c2w_other, w):
+    """depth_cons_loss.py:61-62"""
+    return pose_inverse_4x4_torch(w * pose_c2w_self + (1 - w) * pose_c2w_other)
+
+
+def sample_unseen_pose_torch(poses_w2c, id_self, w):
+    """The pose preparation of DepthConsistencyLoss.compute_loss (depth_cons_loss.py:168-174, :187-188) and sample_pose (:45-63) on
+    poses_w2c [B,3,4] or [B,4,4], detached as the reference detaches them, in the reference's torch operations; the nearest search is
+    `nearest_other_pose_torch`, with no numpy round trip.  -> edict(pose_w2c_ref, pose_c2w_ref, pose_c2w_other, pose_w2c_at_unseen [4,4];
+    id_other, 0-dim int32 on the poses' device)."""
+    from .edict import EasyDict as edict
+    poses = poses_w2c.detach()
+    if poses.shape[1] == 3:
+        poses = torch.cat((poses, poses.new_tensor([0., 0., 0., 1.]).reshape(1, 1, 4).repeat(len(poses), 1, 1)), dim=1)
+    poses_c2w = _pose_inverse_batched_torch(poses)
+    id_other = nearest_other_pose_torch(poses_c2w[:, :3, 3], int(id_self))
+    pose_w2c_ref = poses[id_self]
+    pose_c2w_other = poses_c2w.index_select(0, id_other.long().reshape(1))[0]
+    unseen = _blend_and_invert_torch(pose_inverse_4x4_torch(pose_w2c_ref), pose_c2w_other, w)
+    return edict(pose_w2c_ref=pose_w2c_ref, pose_c2w_ref=poses_c2w[id_self], pose_c2w_other=pose_c2w_other, pose_w2c_at_unseen=unseen, id_other=id_other)
+
+
+def sample_unseen_pose(poses_w2c, id_self, w):
+    """An unseen pose between camera id_self and its nearest other camera, as DepthConsistencyLoss prepares and samples it: the four
+    matrices and the index of `sample_unseen_pose_torch`, in one launch (ops.unseen_pose) and without a readback for float32 poses on
+    the GPU that ask for no gradient; everything else takes the restatement."""
+    from .edict import EasyDict as edict
+    if _unfused or not (_on_gpu(poses_w2c.device) and poses_w2c.dtype == torch.float32 and poses_w2c.layout == torch.strided
+                        and not (poses_w2c.requires_grad and torch.is_grad_enabled())):
+        return sample_unseen_pose_torch(poses_w2c, id_self, w)
+    out, id_other = ops.unseen_pose(poses_w2c, id_self, w)
+    return edict(pose_w2c_ref=out[0], pose_c2w_ref=out[1], pose_c2w_other=out[2], pose_w2c_at_unseen=out[3], id_other=id_other[0])
+
+
+# ---------------------------------------------------------------------------------------------- under the reference's names
+def sample_pose(self, poses_c2w, id_self, pose_w2c_self):
+    """DepthConsistencyLoss.sample_pose (depth_cons_loss.py:45-63) under its own signature: the camera-to-world poses are what it is
+    handed, so the nearest search runs on their centres (`nearest_other_pose_torch`) and the blend and the inverse in the reference's
+    operations; one np.random.rand(), as there; no readback.  -> pose_w2c_at_unseen [4,4]"""
+    id_other = nearest_other_pose_torch(poses_c2w.detach()[:, :3, 3], int(id_self))
+    w = np.random.rand()
+    pose_c2w_other = poses_c2w.detach().index_select(0, id_other.long().reshape(1))[0]
+    return _blend_and_invert_torch(pose_inverse_4x4_torch(pose_w2c_self).detach(), pose_c2w_other, w)
+
+
+def _dcons_starts(opt, iteration):
+    start = opt.start_ratio.depth_cons * opt.max_iter if opt.start_ratio.depth_cons is not None else opt.start_iter.depth_cons
+    return iteration >= start
+
+
+def _at_sampled_pose(self, data_dict, prep, pixels, depth_ref, intr_ref, H, W):
+    """depth_cons_loss.py:115-125, :209-217: the pseudo ground-truth points, then whatever compute_loss_at_sampled_pose the class holds"""
+    points = backproject_to_3d_torch(pixels, depth_ref, intr_ref, prep.pose_c2w_ref)
+    return self.compute_loss_at_sampled_pose(data_dict, pose_w2c_at_unseen=prep.pose_w2c_at_unseen, intr_at_unseen=intr_ref.clone(),
+                                             pseudo_gt_3dpts_in_w=points, H=H, W=W, pixels_in_ref=pixels)
+
+
+def compute_loss_from_existing_pixels(self, opt, data_dict, iteration, pixels_in_ref, id_ref, depth_ref=None):
+    """DepthConsistencyLoss.compute_loss_from_existing_pixels (depth_cons_loss.py:65-125) under its own signature and return convention;
+    its one draw is np.random.rand()"""
+    if not _dcons_starts(opt, iteration):
+        return {}, {}, {}
+    B, _, H, W = data_dict.image.shape
+    prep = sample_unseen_pose(data_dict.poses_w2c.detach(), id_ref, np.random.rand())
+    return _at_sampled_pose(self, data_dict, prep, pixels_in_ref, depth_ref, data_dict.intr[id_ref], H, W)
+
+
+def dcons_compute_loss(self, opt, data_dict, output_dict, iteration, mode=None, plot=False, **kwargs):
+    """DepthConsistencyLoss.compute_loss (depth_cons_loss.py:128-217) under its own signature and return convention.  The draws are the
+    reference's, in its order: np.random.randint(B), the one or two CPU torch.randperm of sample_rays, and -- behind the reference render,
+    as there -- np.random.rand().  Between entry and that render: one copy of the permutation prefix to the device and one launch; the
+    render takes poses_w2c[id_self] where it lies; behind it one launch leaves every matrix.  Nothing is read back."""
+    if mode != 'train':
+        return {}, {}, {}
+    if not _dcons_starts(opt, iteration):
+        return {}, {}, {}
+    B, _, H, W = data_dict.image.shape
+    poses_w2c = data_dict.poses_w2c.detach()
+    id_self = np.random.randint(B)
+    pixels_ref, _ = sample_pixels(H, W, nbr=max(1024, self.opt.nerf.rand_rays), fraction_in_center=self.opt.sampled_fraction_in_center,
+                                  device=self.device)
+    intr_ref = data_dict.intr[id_self]
+    ret_ref = self.net.render_image_at_specific_pose_and_rays(self.opt, data_dict, pose=poses_w2c[id_self][:3], intr=intr_ref, H=H, W=W,
+                                                              pixels=pixels_ref, mode='train', iter=iteration)
+    fine = 'depth_fine' in ret_ref.keys()
+    if fine and hasattr(opt.nerf, 'ratio_start_fine_sampling_at_x') and opt.nerf.ratio_start_fine_sampling_at_x is not None \
+            and iteration < opt.max_iter * (opt.nerf.ratio_start_fine_sampling_at_x + 0.05):
+        fine = False
+    depth_ref = (ret_ref.depth_fine if fine else ret_ref.depth).squeeze(0).squeeze(-1)
+    prep = sample_unseen_pose(poses_w2c, id_self, np.random.rand())
+    return _at_sampled_pose(self, data_dict, prep, pixels_ref, depth_ref, intr_ref, H, W)
+
+
+DCONS_SAMPLER_METHODS = {"sample_pose": sample_pose, "compute_loss": dcons_compute_loss,
+                         "compute_loss_from_existing_pixels": compute_loss_from_existing_pixels}
+_dcons_sampler = Patcher("sparf_amd.losses.install_depth_consistency_sampler", "uninstall_depth_consistency_sampler")
+
+
+def install_depth_consistency_sampler(depth_cons_loss_module):
+    """Opt-in, and independent of install_depth_consistency() (the methods here call whatever compute_loss_at_sampled_pose the class
+    holds when they run, so the two compose in either order): put sample_pose, compute_loss and compute_loss_from_existing_pixels on
+    `depth_cons_loss_module.DepthConsistencyLoss` until `uninstall_depth_consistency_sampler()`.  Nothing in this package calls it."""
+    _dcons_sampler.guard()
+    for name, fn in DCONS_SAMPLER_METHODS.items():
+        _dcons_sampler.put(depth_cons_loss_module.DepthConsistencyLoss, name, fn)
+
+
+def uninstall_depth_consistency_sampler():
+    _dcons_sampler.restore()
+
+
+RAY_SAMPLER_METHOD = "__call__"
+_ray_sampler = Patcher("sparf_amd.losses.install_ray_sampler", "uninstall_ray_sampler")     # keeps the class's own __call__: the in-mask configs are handed to it
+
+
+def ray_sampler_call(self, nbr_pixels, sample_in_center=False, idx_imgs=None):
+    """RaySamplingStrategy.__call__ (sampling_strategies.py:132-188) under its own signature: the same device torch.randperm draws, the
+    centre fraction's before the main one, and the same rays, in one launch (ops.pick_pixels) instead of two index operations, the patch
+    expansion and the ray arithmetic.  The pools are rectangles: the grid behind self.all_possible_pixels and the centre box behind
+    self.all_center_pixels.  A config with sample_fraction_in_fg_mask > 0, a sampler off the GPU and pools of another size than their
+    rectangles are handed to the original method."""
+    original = _ray_sampler.original(RAY_SAMPLER_METHOD)
+    opt, H, W = self.opt, self.H, self.W
+    dev = ops._resolve(self.device)
+    patch = opt.depth_regu_patch_size if opt.loss_weight.depth_patch is not None else None
+    p = 1 if patch is None else int(patch)
+    a_w, a_h = (W, H) if patch is None else (W - p - 1, H - p - 1)
+    box = _centre_box(H, W, opt.precrop_frac)
+    if (opt.sample_fraction_in_fg_mask > 0. or _unfused or not _on_gpu(dev) or a_w <= 0 or a_h <= 0 or len(self.all_possible_pixels) != a_w * a_h
+            or len(self.all_center_pixels) != box[2] * box[3] or box[2] <= 0 or box[3] <= 0 or box[0] + box[2] + p - 1 > W):
+        return original(self, nbr_pixels, sample_in_center=sample_in_center, idx_imgs=idx_imgs)
+    nbr_images = self.nbr_images if idx_imgs is None else len(idx_imgs)
+    n_rand = nbr_pixels // nbr_images
+    if patch is not None:
+        n_rand = n_rand // p ** 2
+    perm_center = None
+    if opt.sampled_fraction_in_center > 0:
+        n_center = int(n_rand * opt.sampled_fraction_in_center)
+        n_rand = n_rand - n_center
+        perm_center = torch.randperm(box[2] * box[3], device=dev)[:n_center]
+    if sample_in_center:                                # the main picks are of the centre box too, and come first
+        perm = torch.randperm(box[2] * box[3], device=dev)[:n_rand]
+        perm_a, perm_b = None, perm if perm_center is None else torch.cat((perm, perm_center))
+    else:
+        perm_a, perm_b = torch.randperm(a_w * a_h, device=dev)[:n_rand], perm_center
+    return ops.pick_pixels(perm_a, perm_b, (a_w, a_h), box, W, p, pixels=False, device=dev)[1]
+
+
+def install_ray_sampler(sampling_module):
+    """Opt-in, and independent of the other installs: put the method above on `sampling_module.RaySamplingStrategy` until
+    `uninstall_ray_sampler()`.  Nothing in this package calls it."""
+    _ray_sampler.guard()
+    cls = sampling_module.RaySamplingStrategy
+    _ray_sampler.save(RAY_SAMPLER_METHOD, cls.__call__)
+    _ray_sampler.put(cls, RAY_SAMPLER_METHOD, ray_sampler_call)
+
+
+def uninstall_ray_sampler():
+    _ray_sampler.restore()

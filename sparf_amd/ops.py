@@ -1374,6 +1374,73 @@ def ray_depth_err(depth_gt, valid_depth_gt, depth, depth_fine=None, ray_idx=None
     return out, count
 
 
+# ---------------------------------------------------------------------------------------------- pixel picks and the unseen pose
+PICK_MAX_ROWS = 1 << 30          # csrc/pick.hip kPickMaxRows
+
+
+def _pick_perm(perm, name, dev):
+    if perm is None:
+        return None, 0
+    if perm.dtype != torch.int64 or perm.dim() != 1 or _resolve(perm.device) != dev:
+        raise ValueError(f"pick pixels: {name} must be int64 [n] on {dev}, got {perm.dtype} {list(perm.shape)} on {perm.device}")
+    return (perm.detach().contiguous(), perm.numel()) if perm.numel() else (None, 0)
+
+
+def pick_pixels(perm_a, perm_b, pool_a, pool_b, W, patch=1, *, pixels=True, rays=True, device=None):
+    """sparf_pick_pixels: perm_a / perm_b int64 [n] on the device (None or empty: no pick of that pool) index pool_a = (a_w, a_h), the
+    grid [0,a_w) x [0,a_h), and pool_b = (b_x0, b_y0, b_w, b_h), a box, both row-major (None: (0, 0) / (0, 0, 0, 0)); an entry outside its
+    pool is clamped into it.  -> (pixels float32 [(n_a + n_b) patch^2, 2] = (x, y), rays int64 [...] = y W + x), the picks of A before those
+    of B, each expanded by the patch offsets (dy outer, dx inner); an output not asked for is None: one launch, no readback"""
+    dev = device if device is not None else next((t.device for t in (perm_a, perm_b) if t is not None), None)
+    if dev is None:
+        raise ValueError("pick pixels: no permutation and no device")
+    dev = _resolve(dev)                                   # (a bare 'cuda', as the reference trainer holds it, is the current device)
+    L.require_gpu(dev)
+    pa, n_a = _pick_perm(perm_a, "perm_a", dev)
+    pb, n_b = _pick_perm(perm_b, "perm_b", dev)
+    a_w, a_h = (int(v) for v in (pool_a or (0, 0)))
+    b_x0, b_y0, b_w, b_h = (int(v) for v in (pool_b or (0, 0, 0, 0)))
+    W, patch = int(W), int(patch)
+    if W <= 0 or not 1 <= patch <= 1024:
+        raise ValueError(f"pick pixels: W must be positive and patch in [1, 1024], got W {W} patch {patch}")
+    rows = (n_a + n_b) * patch * patch
+    if rows > PICK_MAX_ROWS:
+        raise ValueError(f"pick pixels: {rows} rows, at most 2^30")
+    for n, x0, y0, w, h, name in ((n_a, 0, 0, a_w, a_h, "A"), (n_b, b_x0, b_y0, b_w, b_h, "B")):
+        if n and (x0 < 0 or y0 < 0 or w <= 0 or h <= 0 or w * h > PICK_MAX_ROWS or x0 + w + patch - 1 > W):
+            raise ValueError(f"pick pixels: pool {name} ({x0}, {y0}, {w}, {h}) with a patch of {patch} does not lie in rows of {W} pixels")
+    out_px = torch.empty(rows, 2, device=dev, dtype=torch.float32) if pixels else None
+    out_rays = torch.empty(rows, device=dev, dtype=torch.int64) if rays else None
+    if rows and (pixels or rays):
+        p = L.ptr
+        L.call("sparf_pick_pixels", dev, p(pa), n_a, p(pb), n_b, a_w, a_h, b_x0, b_y0, b_w, b_h, W, patch, p(out_px), p(out_rays))
+    return out_px, out_rays
+
+
+UNSEEN_POSE_OUTS = ("pose_w2c_ref", "pose_c2w_ref", "pose_c2w_other", "pose_w2c_at_unseen")
+
+
+def unseen_pose(poses_w2c, id_self, w):
+    """sparf_unseen_pose: poses_w2c float32 [B,3,4] or [B,4,4] on the device, id_self an int in [0, B), w a number (1 - w is taken in
+    double and rounded to float32 once, as torch handles the scalar).  -> (out float32 [4,4,4]: pose_w2c_ref, pose_c2w_ref,
+    pose_c2w_other, pose_w2c_at_unseen; id_other int32 [1]) on the device: one launch, no readback"""
+    op = "unseen pose"
+    if poses_w2c.dtype != torch.float32 or poses_w2c.dim() != 3 or tuple(poses_w2c.shape[1:]) not in ((3, 4), (4, 4)) or poses_w2c.shape[0] < 1:
+        raise ValueError(f"{op}: poses_w2c must be float32 [B,3,4] or [B,4,4] of at least one pose, got {poses_w2c.dtype} {list(poses_w2c.shape)}")
+    dev = poses_w2c.device
+    L.require_gpu(dev)
+    B, id_self, w = poses_w2c.shape[0], int(id_self), float(w)
+    if not 0 <= id_self < B:
+        raise ValueError(f"{op}: id_self {id_self} outside [0, {B})")
+    poses = poses_w2c.detach()
+    poses = poses if poses.is_contiguous() else poses.contiguous()
+    out = torch.empty(len(UNSEEN_POSE_OUTS), 4, 4, device=dev, dtype=torch.float32)
+    id_other = torch.empty(1, device=dev, dtype=torch.int32)
+    p = lambda k: ctypes.c_void_p(out.data_ptr() + 64 * k)
+    L.call("sparf_unseen_pose", dev, L.ptr(poses), poses.shape[1] * 4, B, id_self, w, 1.0 - w, p(0), p(1), p(2), p(3), L.ptr(id_other))
+    return out, id_other
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone compositing
 class Composite(torch.autograd.Function):
     """NeRF.composite (frequency_nerf.py:283-343) on caller-built per-sample values (C ABI 6 sparf_composite_forward / _backward):
