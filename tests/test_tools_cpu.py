@@ -179,3 +179,143 @@ def test_shipped_kernels_have_no_experiment_or_probe_flag_on():
         assert name in text, f"{name}: the instrument is gone from the sources"
         assert not re.search(r"^\s*#\s*define\s+%s\b" % name, text, flags=re.M), f"{name} is defined in the sources"
         assert not any(name in f for f in B.FLAGS), f"{name} is passed by the default build"
+
+
+# ---- tools/paired_bench.py: the measurement scheme of the eleven comparison benches
+PAIRED_TOOLS = ("colmap_depth_bench", "corres_loss_bench", "dcons_front_bench", "depth_cons_bench", "depth_err_bench", "image_metrics_bench",
+                "match_select_bench", "photo_loss_bench", "pose_eval_bench", "pose_optim_bench", "test_optim_bench")
+
+
+def _paired():
+    return _load("tools/paired_bench.py", "paired_bench")
+
+
+def test_paired_bench_alternate_warms_every_leg_up_then_alternates_the_blocks():
+    pb = _paired()
+    calls = []
+
+    def block(work, iters):
+        calls.append((work, iters))
+        return len(calls)
+
+    got = pb.alternate({"a": "A", "b": "B", "c": "C"}, blocks=2, iters=7, warmup=3, block=block)
+    assert calls == [("A", 3), ("B", 3), ("C", 3)] + [("A", 7), ("B", 7), ("C", 7)] * 2
+    assert got == {"a": [4, 7], "b": [5, 8], "c": [6, 9]}
+    assert list(got) == ["a", "b", "c"]
+
+
+def test_paired_bench_records_and_the_leg_against_its_baseline():
+    import math
+    pb = _paired()
+    base, other = [4.0, 1.0, 3.0, 2.0], [0.5, 1.0, 0.25, 0.75]          # an even number of blocks: the median is the mean of the middle two
+    assert pb.flat(base) == dict(ms_per_iter_median=2.5, ms_per_iter_min=1.0, ms_per_iter_max=4.0, ms_per_iter_blocks=base)
+    assert list(pb.flat(base)) == ["ms_per_iter_median", "ms_per_iter_min", "ms_per_iter_max", "ms_per_iter_blocks"]
+    assert pb.summary(other) == dict(median=0.625, min=0.25, max=1.0, blocks=other)
+    assert list(pb.summary(other)) == ["median", "min", "max", "blocks"]
+    assert pb.versus(base, other) == (0.25, 1.875, True)                   # other.max == base.min: they overlap
+    below = [0.5, math.nextafter(1.0, 0.0), 0.25, 0.75]                   # one ulp below: they do not
+    assert pb.versus(base, below)[2] is False
+    assert pb.versus(base, [5.0, 6.0]) == (2.2, -3.0, True)
+
+
+def test_paired_bench_activities_sorts_the_names_of_a_traced_window():
+    pb = _paired()
+    long = "void sparf::ordered_sum_single_kernel<sparf::DepthErr>(" + "x" * 80 + ")"
+    device = ["short_kernel", "Memcpy DtoH (Device -> Pinned)", long, "Memcpy HtoD (Pageable -> Device)", "Memset (Device)"]
+    host = ["aten::nonzero", "aten::_local_scalar_dense", "hipStreamSynchronize", "aten::_local_scalar_dense", "hipMemcpyWithStream", "hipMemcpyAsync",
+            "hipDeviceSynchronize"]
+    for every in (False, True):
+        t = pb.activities(device, host, every_device_sync=every)
+        assert t.kernels == ["short_kernel", long]
+        assert t.copies == [device[1], device[3], device[4]]
+        assert t.copies_by_label == {device[1]: 1, device[3]: 1, device[4]: 1} and list(t.copies_by_label) == sorted(t.copies)
+        assert (t.host_to_device, t.readbacks_by_label, t.readbacks_asked) == (1, 1, 3)
+        assert t.host_waits == ["hipMemcpyWithStream", "hipStreamSynchronize"]
+        assert t.by_name == {"short_kernel": 1, long[:80]: 1} and [len(k) for k in t.by_name] == [12, 80]
+    # no closing synchronise in the list: nothing is removed; the profiler's own second one stays unless every one is asked out
+    assert pb.activities([], host[:-1]).host_waits == ["hipMemcpyWithStream", "hipStreamSynchronize"]
+    twice = host + ["hipDeviceSynchronize"]
+    assert pb.activities([], twice).host_waits == ["hipDeviceSynchronize", "hipMemcpyWithStream", "hipStreamSynchronize"]
+    assert pb.activities([], twice, every_device_sync=True).host_waits == ["hipMemcpyWithStream", "hipStreamSynchronize"]
+    assert pb.activities(device, []).readbacks_asked == 0                     # a device-only trace asks for none
+
+
+def test_paired_bench_existing_and_emit(tmp_path, capsys):
+    import json
+    pb = _paired()
+    out = str(tmp_path / "not" / "there" / "doc.json")
+    assert pb.existing(out, dict(rows={})) == dict(rows={}) and pb.existing(None, 5) == 5
+    doc = dict(tool="t", rows=dict(a=dict(n=1)))
+    pb.emit(doc, out)                                                         # the missing directory is created
+    text = json.dumps(doc, indent=1)
+    assert capsys.readouterr().out == text + "\n" and open(out).read() == text + "\n"
+    again = pb.existing(out, dict(rows={}))                                   # a --trace-only style update keeps the keys already there
+    again["rows"].setdefault("a", {})["traced"] = dict(kernels=2)
+    pb.emit(again, out, one_line=True)
+    assert capsys.readouterr().out == json.dumps(again) + "\n" and "\n" not in json.dumps(again)
+    assert open(out).read() == json.dumps(again, indent=1) + "\n"
+    assert json.load(open(out)) == dict(tool="t", rows=dict(a=dict(n=1, traced=dict(kernels=2))))
+    pb.emit(doc, None)                                                        # no --out: stdout alone
+    assert capsys.readouterr().out == text + "\n"
+
+
+def test_paired_bench_diff_prints_what_differs_and_is_no_timing(tmp_path, capsys):
+    import copy
+    import json
+    pb = _paired()
+    a = dict(tool="t", label="parent", device="gpu A", blocks=2, legs=["series", "fused"],
+             rows=dict(r=dict(series=dict(ms_per_iter_median=1.5, ms_per_iter_blocks=[1.0, 2.0], device_ms_per_iter=dict(median=1.5, blocks=[1.0, 2.0])),
+                              fused_over_series=0.5, blocks_overlap=False, result=dict(loss=0.25, count=7),
+                              traced=dict(kernels=3, copies_and_memsets=2, by_name={"k": 3}))))
+    b = copy.deepcopy(a)
+    b.update(label="branch", device="gpu B")
+    r = b["rows"]["r"]
+    r["series"].update(ms_per_iter_median=1.75, ms_per_iter_blocks=[1.5, 2.0, 2.5], device_ms_per_iter=dict(median=9.0, blocks=[9.0]))
+    r.update(fused_over_series=0.75, blocks_overlap=True)
+    assert pb.diff(a, b) == []                                                # timings, label and device alone
+    paths = {name: str(tmp_path / f"{name}.json") for name in "abc"}
+    for name, doc in zip("ab", (a, b)):
+        json.dump(doc, open(paths[name], "w"))
+    assert pb.main(["diff", paths["a"], paths["b"]]) == 0 and capsys.readouterr().out == ""
+    del r["traced"]["by_name"]                                                # a missing key, a new key, two changed counts
+    r["traced"]["copies_and_memsets"] = 4
+    r["result"].update(count=8, more=1)
+    b["legs"].append("body")
+    lines = pb.diff(a, b)
+    assert lines == ["only in A: rows/r/traced/by_name/k", "only in B: legs/2", "only in B: rows/r/result/more",
+                     "differs: rows/r/result/count: 7 != 8", "differs: rows/r/traced/copies_and_memsets: 2 != 4"]
+    c = copy.deepcopy(a)                                                      # a second run of A's tree: its count is not the same from run to run
+    c["rows"]["r"]["result"]["count"] = 9
+    assert pb.diff(a, b, like=c) == [x for x in lines if "result/count" not in x]
+    for name, doc in zip("bc", (b, c)):
+        json.dump(doc, open(paths[name], "w"))
+    assert pb.main(["diff", paths["a"], paths["b"], "--like", paths["c"]]) == 1
+    assert capsys.readouterr().out.splitlines() == pb.diff(a, b, like=c)
+
+
+def test_paired_tools_hold_no_timing_or_profiler_scheme_of_their_own():
+    """The eleven comparison benches take their blocks, their records and their profiler pass from tools/paired_bench.py (a twelfth
+    bench with legs belongs in the list): none times with device events, opens the profiler or takes a median itself."""
+    for tool in PAIRED_TOOLS:
+        text = open(os.path.join(ROOT, "tools", tool + ".py")).read()
+        assert "import paired_bench" in text, f"{tool} does not import paired_bench"
+        for word in ("torch.cuda.Event", "torch.profiler", "statistics."):
+            assert word not in text, f"{tool} has a {word} of its own: the scheme lives in tools/paired_bench.py"
+    shared = open(os.path.join(ROOT, "tools", "paired_bench.py")).read()
+    assert all(word in shared for word in ("torch.cuda.Event", "torch.profiler", "statistics."))
+
+
+def test_paired_tools_load_and_fail_without_a_device(monkeypatch):
+    """A measuring path that finds no GPU fails, it does not fall back: main() ends in the SystemExit that names the tool."""
+    import pytest
+    from sparf_amd import lib as L
+    if not os.path.exists(L.LIB_PATH):
+        pytest.skip("libsparf_hip.so is not built")
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)           # (on a machine with a device: what the tools ask)
+    monkeypatch.syspath_prepend(os.path.join(ROOT, "tools"))
+    for tool in PAIRED_TOOLS:
+        m = _load(f"tools/{tool}.py", tool + "_loaded")
+        monkeypatch.setattr("sys.argv", [f"tools/{tool}.py"])
+        with pytest.raises(SystemExit) as e:
+            m.main()
+        assert str(e.value) == f"tools/{tool}.py measures on the GPU: no device found"

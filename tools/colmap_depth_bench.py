@@ -12,24 +12,22 @@ one readback, per image its randperm, its gather and its deferred render, one ba
 Rows, for B in {3, 6, 9} images of 300 x 400 with rand_rays = 2048 (quota 682 / 341 / 227) on COLMAP maps that hold a depth at about
 2 % of the pixels (about 2400 per image: every image draws): `alone_B<B>`: the method with a stand-in render (a depth that is an
 elementwise function of ray_idx, no network); `whole_B<B>`: around a real Graph in bf16x3 at 64 + 128 samples, with the backward to
-the networks.  Both legs of a row run in ONE process in alternating blocks of `--iters` iterations (ten times as many in an `alone`
-row) after a warm-up of each; per leg ms per iteration (device events around a block; the readbacks stall the host inside the block,
-so the figure is wall time as the device saw it) as median and min ... max over the blocks, `installed` over `series`, and whether
+the networks.  Both legs of a row run in the alternating blocks of tools/paired_bench.py, of `--iters` iterations (ten times as many
+in an `alone` row); per leg ms per iteration as median and min ... max over the blocks, `installed` over `series`, and whether
 their blocks overlap.  After the timed blocks each leg runs one more iteration from the same seed under counters: the host readbacks
 it made (single-argument torch.where calls, .item() and .tolist()), its render calls and how many launch sets they became; the loss and
 the ray lists' checksum are reported.  `--trace-only` (a run of its own: tracing slows the host) times nothing: it traces ONE iteration
-of each leg of every row after the warm-up with the profiler and reports the kernels, copies and memsets it launched and the runtime's
-synchronising calls, under `traced_iteration`.  One JSON document on stdout and, with --out, in that file (a --trace-only run adds its
+of each leg of every row after the warm-up (paired_bench's profiler pass) and reports the kernels, copies and memsets it launched and
+the host waits, under `traced_iteration`.  One JSON document on stdout and, with --out, in that file (a --trace-only run adds its
 key to the document already there)."""
-import argparse
 import contextlib
-import json
 import os
-import statistics
 import sys
 import types
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -113,18 +111,6 @@ class Work:
         return dict(loss=float(self.report["loss"]), perc_col_depth=self.report["perc_col_depth"])
 
 
-def block(work, iters):
-    """-> ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 @contextlib.contextmanager
 def counters(work):
     """the host readbacks and the render calls of what runs inside"""
@@ -162,33 +148,14 @@ def counters(work):
 
 
 def traced(work):
-    """-> the device activities of ONE iteration, from the profiler's trace: kernels, copies and memsets, and the runtime calls that make
-    the host wait (synchronisations and blocking copies)"""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        work.iteration()
-        torch.cuda.synchronize()
-    events = list(prof.events())
-    names = [e.name for e in events if str(e.device_type).endswith("CUDA")]
-    copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-    waits = [e.name for e in events if not str(e.device_type).endswith("CUDA") and e.name.startswith(("hip", "cuda")) and
-             ("Synchronize" in e.name or ("Memcpy" in e.name and "Async" not in e.name))]
-    for own in ("hipDeviceSynchronize", "cudaDeviceSynchronize"):           # the one that ends the traced window
-        if own in waits:
-            waits.remove(own)
-            break
-    return dict(kernels=len(names) - len(copies), copies_and_memsets=len(copies), host_waits=len(waits), host_waits_by_name=sorted(waits))
+    """-> the device activities of ONE iteration (paired_bench.traced): kernels, copies and memsets, and the host waits"""
+    t = pb.traced(work.iteration, host=True)
+    return dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies), host_waits=len(t.host_waits), host_waits_by_name=t.host_waits)
 
 
 def measure(works, blocks, iters, warmup):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    ms = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            ms[k].append(block(w, iters))
-    out = {k: dict(ms_per_iter_median=statistics.median(t), ms_per_iter_min=min(t), ms_per_iter_max=max(t), ms_per_iter_blocks=t) for k, t in ms.items()}
+    ms = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: pb.flat(t) for k, t in ms.items()}
     out["result"], out["counts"] = {}, {}
     for k, w in works.items():                                 # the reported iteration: every leg from the same generator state
         torch.manual_seed(0)
@@ -196,50 +163,37 @@ def measure(works, blocks, iters, warmup):
             w.iteration()
             torch.cuda.synchronize()
         out["result"][k], out["counts"][k] = w.result(), c
-    out["installed_over_series"] = out["installed"]["ms_per_iter_median"] / out["series"]["ms_per_iter_median"]
-    out["installed_and_series_blocks_overlap"] = out["installed"]["ms_per_iter_max"] >= out["series"]["ms_per_iter_min"]
-    out["series_minus_installed_ms"] = out["series"]["ms_per_iter_median"] - out["installed"]["ms_per_iter_median"]
+    ratio, less, overlap = pb.versus(ms["series"], ms["installed"])
+    out.update(installed_over_series=ratio, installed_and_series_blocks_overlap=overlap, series_minus_installed_ms=less)
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__, iters=10, warmup=3)
     ap.add_argument("--rows", nargs="+", default=["alone", "whole"], choices=["alone", "whole"])
     ap.add_argument("--batches", nargs="+", type=int, default=[3, 6, 9])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trace-only", action="store_true", help="trace one iteration of each leg with the profiler; time nothing")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/colmap_depth_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/colmap_depth_bench.py")
     rows = {}
     for B in a.batches:
         for kind in a.rows:
             works = {leg: Work(leg, B, device, kind == "whole") for leg in LEGS}
             if a.trace_only:
                 for w in works.values():
-                    block(w, a.warmup)
+                    pb.device_block(w, a.warmup)
                 rows[f"{kind}_B{B}"] = {leg: traced(w) for leg, w in works.items()}
             else:
                 rows[f"{kind}_B{B}"] = measure(works, a.blocks, a.iters * (ALONE_ITERS if kind == "alone" else 1), a.warmup)
     if a.trace_only:
-        doc = json.load(open(a.out)) if a.out and os.path.exists(a.out) else dict(tool="tools/colmap_depth_bench.py --trace-only")
+        doc = pb.existing(a.out, dict(tool="tools/colmap_depth_bench.py --trace-only"))
         doc["traced_iteration"] = rows
     else:
         doc = dict(tool="tools/colmap_depth_bench.py", label=a.label, device=torch.cuda.get_device_name(0),
                    workload=f"SparseCOLMAPDepthLoss.compute_loss on B maps of {H} x {W} with a depth at ~2 % of the pixels, rand_rays = {RAND_RAYS}; "
                             "alone_B<B>: with a stand-in render; whole_B<B>: around a real Graph (bf16x3, 64 + 128 samples) with its backward",
                    blocks=a.blocks, iters_per_block=a.iters, alone_iters_per_block=ALONE_ITERS * a.iters, warmup_iters=a.warmup, legs=list(LEGS), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -9,18 +9,17 @@ composition in torch, then four `losses.reprojection_loss` calls (one launch eac
 Rows.  `alone_<n>`: the loss forward + backward on fixed inputs, n = 1024 and 2048 matches (rand_rays // 2 of the 2048 / 4096 settings),
 gradients to the four depth tensors and both poses.  `iteration_2048`: two 2048-pixel renders at 64 + 128 samples through ONE
 `render_batch` in bf16x3, the loss on their depths (huber, both checks on), backward to both poses and both networks.
-Every leg of a row runs in ONE process in alternating blocks of `--iters` iterations after a warm-up of each; per leg ms per iteration
-(device events around a block) as median and min ... max over the blocks, and `pair` over `series` with whether their blocks overlap.
-`--count-launches` (a run of its own) traces ONE loss-alone iteration of each leg after the warm-up with the profiler's kernel trace and
+The legs of a row run in the alternating blocks of tools/paired_bench.py, of `--iters` iterations; per leg ms per iteration as median
+and min ... max over the blocks, and `pair` over `series` with whether their blocks overlap.
+`--count-launches` (a run of its own) traces ONE loss-alone iteration of each leg after the warm-up (paired_bench's profiler pass) and
 reports the kernels, copies and memsets it launched; it times nothing.
 One JSON document on stdout and, with --out, in that file."""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -122,80 +121,40 @@ class Iteration:
         return loss
 
 
-def block(work, iters):
-    """-> ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def measure(works, blocks, iters, warmup):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    ms = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            ms[k].append(block(w, iters))
-    out = {k: dict(ms_per_iter_median=statistics.median(t), ms_per_iter_min=min(t), ms_per_iter_max=max(t), ms_per_iter_blocks=t) for k, t in ms.items()}
+    ms = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: pb.flat(t) for k, t in ms.items()}
     out["loss"] = {k: float(w.iteration().detach()) for k, w in works.items()}
-    if "series" in out and "pair" in out:
-        out["pair_over_series"] = out["pair"]["ms_per_iter_median"] / out["series"]["ms_per_iter_median"]
-        out["pair_and_series_blocks_overlap"] = out["pair"]["ms_per_iter_max"] >= out["series"]["ms_per_iter_min"]
-        out["series_minus_pair_ms"] = out["series"]["ms_per_iter_median"] - out["pair"]["ms_per_iter_median"]
+    if "series" in ms and "pair" in ms:
+        ratio, less, overlap = pb.versus(ms["series"], ms["pair"])
+        out.update(pair_over_series=ratio, pair_and_series_blocks_overlap=overlap, series_minus_pair_ms=less)
     return out
 
 
 def count_launches(device, legs, n, warmup):
-    """-> per leg the device activities of ONE loss-alone iteration (forward + backward) after the warm-up, from the profiler's kernel
-    trace: kernels, memory copies and memsets, with the kernels' names"""
-    from torch.profiler import ProfilerActivity, profile
+    """-> per leg the device activities of ONE loss-alone iteration (forward + backward) after the warm-up (paired_bench.traced):
+    kernels, memory copies and memsets, with the kernels' names"""
     works = {leg: Alone(leg, n, device) for leg in legs}
     for w in works.values():
-        block(w, warmup)
+        pb.device_block(w, warmup)
     out = {}
     for leg, w in works.items():
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            w.iteration()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
-        copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-        kernels = [x for x in names if x not in copies]
-        hist = {}
-        for x in kernels:
-            hist[x[:80]] = hist.get(x[:80], 0) + 1
-        out[leg] = dict(kernels=len(kernels), copies_and_memsets=len(copies), by_name=hist)
+        t = pb.traced(w.iteration)
+        out[leg] = dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies), by_name=t.by_name)
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--legs", nargs="+", default=list(LEGS), choices=LEGS)
     ap.add_argument("--rows", nargs="+", default=["alone", "iteration"], choices=["alone", "iteration"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--count-launches", action="store_true")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/corres_loss_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/corres_loss_bench.py")
     if a.count_launches:
         doc = dict(tool="tools/corres_loss_bench.py --count-launches", device=torch.cuda.get_device_name(0), matches=1024,
                    launches_per_iteration=count_launches(device, a.legs, 1024, a.warmup))
-        text = json.dumps(doc, indent=1)
-        print(text)
-        if a.out:
-            with open(a.out, "w") as f:
-                f.write(text + "\n")
-        return
+        return pb.emit(doc, a.out)
     rows = {}
     if "alone" in a.rows:
         for n in (1024, 2048):
@@ -206,12 +165,7 @@ def main():
                workload="correspondence loss of one view pair, huber with both checks, four terms; alone_<n>: loss forward + backward on fixed "
                         "inputs; iteration_2048: two 2048-pixel renders x (64 + 128) through render_batch in bf16x3, loss, backward",
                blocks=a.blocks, iters_per_block=a.iters, warmup_iters=a.warmup, legs=a.legs, rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

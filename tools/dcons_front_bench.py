@@ -12,26 +12,24 @@ Rows, for B in {3, 6, 9} views of 300 x 400 and 2048 pixels: `alone_B<B>`: the f
 the unseen pose, no render; `loss_B<B>`: the whole compute_loss around its three real renders (64 + 128 samples, bf16x3), the core
 method that of install_depth_consistency() in both legs, with a backward to both networks.  `sampler_<patch>`:
 RaySamplingStrategy.__call__ at 2048 rays over 3 views, without and with loss_weight.depth_patch (patch 2): `series` restates the
-reference's index operations, `installed` is install_ray_sampler()'s.  The legs of a row run in ONE process in alternating,
-non-overlapping blocks of `--iters` iterations (ten times as many in the rows without a render) after a warm-up of each; per leg ms per
-iteration (device events around a block; a readback stalls the host inside the block, so the figure is wall time as the device saw it)
-as median and min ... max over the blocks.  After ALL timing ONE iteration of each leg of the rows without a render is traced with the
-profiler: kernels, copies under the profiler's labels, host-to-device copies, readbacks (an `aten::_local_scalar_dense`, an
-`aten::nonzero` or a device-to-host copy).  `cpu_randperm_ms`: the CPU torch.randperm of the pool, which stays in both legs as the
+reference's index operations, `installed` is install_ray_sampler()'s.  The legs of a row run in the alternating blocks of
+tools/paired_bench.py, of `--iters` iterations (ten times as many in the rows without a render); per leg ms per iteration as median and
+min ... max over the blocks.  After ALL timing ONE iteration of each leg of the rows without a render is traced (paired_bench's
+profiler pass): kernels, copies under the profiler's labels, host-to-device copies, readbacks (where they are asked for plus the
+device-to-host copies: a readback that shows both ways counts twice).  `cpu_randperm_ms`: the CPU torch.randperm of the pool, which stays in both legs as the
 parity contract, timed on the host alone.  `--trace-only` (a run of its own) times nothing: it traces one iteration of each leg of
 EVERY row, the `loss_B<B>` rows included -- there the counts hold the renders' and the core method's launches and the two ray-count
 readbacks of the core method in both legs; the difference between the legs is the front end's.  One JSON document on stdout and, with
 --out, in that file (a --trace-only run adds its key to the rows of the document already there)."""
-import argparse
-import json
 import os
-import statistics
 import sys
 import time
 import types
 
 import numpy as np
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -188,47 +186,20 @@ class Work:
             self.value = loss.detach()
 
 
-def block(work, iters):
-    """-> ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def traced(work):
-    """-> the device activities of ONE iteration from the profiler's trace"""
-    from torch.profiler import ProfilerActivity, profile
+    """-> the device activities of ONE iteration (paired_bench.traced); a readback counts where it is asked for AND as its copy"""
     np.random.seed(1)                                          # the same draws in every leg: the same view, pixels and blend
     torch.manual_seed(1)
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        work.iteration()
-        torch.cuda.synchronize()
-    events = list(prof.events())
-    names = [e.name for e in events if str(e.device_type).endswith("CUDA")]
-    copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-    host = [e.name for e in events if not str(e.device_type).endswith("CUDA")]
-    readbacks = sum(1 for x in host if x in ("aten::nonzero", "aten::_local_scalar_dense")) + sum(1 for x in copies if "DtoH" in x)
-    return dict(launches=len(names) - len(copies), copies_and_memsets=len(copies), copies_by_label={x: copies.count(x) for x in sorted(set(copies))},
-                host_to_device_copies=sum(1 for x in copies if "HtoD" in x), readbacks=readbacks)
+    t = pb.traced(work.iteration, host=True)
+    return dict(launches=len(t.kernels), copies_and_memsets=len(t.copies), copies_by_label=t.copies_by_label, host_to_device_copies=t.host_to_device,
+                readbacks=t.readbacks_asked + t.readbacks_by_label)
 
 
 def measure(works, blocks, iters, warmup, trace):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    ms = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            ms[k].append(block(w, iters))
-    out = {k: dict(ms_per_iter_median=statistics.median(t), ms_per_iter_min=min(t), ms_per_iter_max=max(t), ms_per_iter_blocks=t) for k, t in ms.items()}
-    out["series_minus_installed_ms"] = out["series"]["ms_per_iter_median"] - out["installed"]["ms_per_iter_median"]
-    out["installed_over_series"] = out["installed"]["ms_per_iter_median"] / out["series"]["ms_per_iter_median"]
-    out["blocks_overlap"] = out["installed"]["ms_per_iter_max"] >= out["series"]["ms_per_iter_min"]
+    ms = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: pb.flat(t) for k, t in ms.items()}
+    ratio, less, overlap = pb.versus(ms["series"], ms["installed"])
+    out.update(series_minus_installed_ms=less, installed_over_series=ratio, blocks_overlap=overlap)
     for k, w in works.items():
         if w.counts:                                           # the pixels that entered the core method: the three renders ran
             out[k]["pixels_into_the_core_min_max"] = [min(w.counts), max(w.counts)]
@@ -241,7 +212,7 @@ def trace_only(a, device):
     """a run of its own (tracing slows the host): ONE traced iteration of each leg of EVERY row, the rows around the renders included
     (their counts hold the renders' and the core method's launches in both legs); adds `traced_iteration` to the rows of the document
     already at --out"""
-    doc = json.load(open(a.out)) if a.out and os.path.exists(a.out) else dict(tool="tools/dcons_front_bench.py --trace-only", rows={})
+    doc = pb.existing(a.out, dict(tool="tools/dcons_front_bench.py --trace-only", rows={}))
     names = {}
     for kind in a.rows:
         if kind == "sampler":
@@ -251,13 +222,9 @@ def trace_only(a, device):
     for name, (kind, B, patch) in names.items():
         works = {leg: Work(leg, kind, B, device, patch) for leg in LEGS}
         for w in works.values():
-            block(w, a.warmup)
+            pb.device_block(w, a.warmup)
         doc["rows"].setdefault(name, {})["traced_iteration"] = {leg: traced(w) for leg, w in works.items()}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 def cpu_randperm_ms(n_pool, n, iters=200):
@@ -270,19 +237,12 @@ def cpu_randperm_ms(n_pool, n, iters=200):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--rows", nargs="+", default=["alone", "loss", "sampler"], choices=["alone", "loss", "sampler"])
     ap.add_argument("--batches", nargs="+", type=int, default=[3, 6, 9])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--trace-only", action="store_true", help="trace one iteration of each leg of every row with the profiler; time nothing")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/dcons_front_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/dcons_front_bench.py")
     np.random.seed(0)
     torch.manual_seed(0)
     rows, to_trace = {}, []
@@ -306,12 +266,7 @@ def main():
                         f"RaySamplingStrategy.__call__ at {RAYS} rays over 3 views",
                blocks=a.blocks, iters_per_block=a.iters, short_iters_per_block=SHORT_ITERS * a.iters, warmup_iters=a.warmup, legs=list(LEGS),
                cpu_randperm_ms=dict(pool=(H - 1) * (W - 1), picks=RAYS, ms_per_draw=cpu_randperm_ms((H - 1) * (W - 1), RAYS)), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -10,22 +10,21 @@ Rows.  `chain_<n>`: the three ops and their backward at n = 1024 and 2048 pixels
 per source pixel, gathered through the ops' index; the rendered depth also depends weakly on the pixel, so the backward reaches the
 projection as it does behind a render), gradient to depth_ref.  `whole_2048`: a 2048-pixel render of the reference view at 64 + 128
 samples in bf16x3, project, `render_to_max` under no_grad, select, the render at the kept pixels, the loss, backward to both networks.
-Both legs of a row run in ONE process in alternating blocks of `--iters` iterations after a warm-up of each; per leg ms per iteration
-(device events around a block) as median and min ... max over the blocks, `fused` over `series`, and whether their blocks overlap.
+Both legs of a row run in the alternating blocks of tools/paired_bench.py, of `--iters` iterations; per leg ms per iteration as median
+and min ... max over the blocks, `fused` over `series`, and whether their blocks overlap.
 After the timed blocks each leg runs one more iteration from the same generator seed; its loss and point counts are reported.
 In a chain row the time left in `fused` is mostly the row's own stand-ins for the renders (the gathers through the ops' index and the
 synthetic depths), which both legs run: read the row as the difference of its legs, not `fused` as the cost of the three calls.
-`--count-launches` (a run of its own) traces ONE chain-alone iteration of each leg after the warm-up with the profiler's kernel trace and
+`--count-launches` (a run of its own) traces ONE chain-alone iteration of each leg after the warm-up (paired_bench's profiler pass) and
 reports the kernels, copies and memsets it launched; it times nothing.
 One JSON document on stdout and, with --out, in that file."""
-import argparse
 import contextlib
-import json
 import os
-import statistics
 import sys
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -127,73 +126,38 @@ class Whole:
         return loss
 
 
-def block(work, iters):
-    """-> ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def measure(works, blocks, iters, warmup):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    ms = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            ms[k].append(block(w, iters))
-    out = {k: dict(ms_per_iter_median=statistics.median(t), ms_per_iter_min=min(t), ms_per_iter_max=max(t), ms_per_iter_blocks=t) for k, t in ms.items()}
+    ms = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: pb.flat(t) for k, t in ms.items()}
     out["loss"] = {}
     for k, w in works.items():                                 # the reported iteration: every leg from the same generator state, so the
         torch.manual_seed(0)                                   # renders' stratified draws (and with them depth_ref) are the same in both
         out["loss"][k] = float(w.iteration().detach())
     out["points_after_mask_and_visibility"] = {k: w.counts for k, w in works.items()}
-    out["fused_over_series"] = out["fused"]["ms_per_iter_median"] / out["series"]["ms_per_iter_median"]
-    out["fused_and_series_blocks_overlap"] = out["fused"]["ms_per_iter_max"] >= out["series"]["ms_per_iter_min"]
-    out["series_minus_fused_ms"] = out["series"]["ms_per_iter_median"] - out["fused"]["ms_per_iter_median"]
+    ratio, less, overlap = pb.versus(ms["series"], ms["fused"])
+    out.update(fused_over_series=ratio, fused_and_series_blocks_overlap=overlap, series_minus_fused_ms=less)
     return out
 
 
 def count_launches(device, n, warmup):
-    """-> per leg the device activities of ONE chain-alone iteration (forward + backward) after the warm-up, from the profiler's kernel
-    trace: kernels, memory copies and memsets, with the kernels' names"""
-    from torch.profiler import ProfilerActivity, profile
+    """-> per leg the device activities of ONE chain-alone iteration (forward + backward) after the warm-up (paired_bench.traced):
+    kernels, memory copies and memsets, with the kernels' names"""
     works = {leg: Chain(leg, n, device) for leg in LEGS}
     for w in works.values():
-        block(w, warmup)
+        pb.device_block(w, warmup)
     out = {}
     for leg, w in works.items():
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            w.iteration()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
-        copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-        kernels = [x for x in names if x not in copies]
-        hist = {}
-        for x in kernels:
-            hist[x[:80]] = hist.get(x[:80], 0) + 1
-        out[leg] = dict(kernels=len(kernels), copies_and_memsets=len(copies), by_name=hist)
+        t = pb.traced(w.iteration)
+        out[leg] = dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies), by_name=t.by_name)
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--rows", nargs="+", default=["chain", "whole"], choices=["chain", "whole"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--count-launches", action="store_true")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/depth_cons_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/depth_cons_bench.py")
     if a.count_launches:
         doc = dict(tool="tools/depth_cons_bench.py --count-launches", device=torch.cuda.get_device_name(0), pixels=1024,
                    launches_per_iteration=count_launches(device, 1024, a.warmup))
@@ -209,12 +173,7 @@ def main():
                             "their backward on fixed inputs; whole_2048: reference render, project, render_to_max, select, render, loss, backward "
                             "at 2048 pixels x (64 + 128) in bf16x3",
                    blocks=a.blocks, iters_per_block=a.iters, warmup_iters=a.warmup, legs=list(LEGS), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

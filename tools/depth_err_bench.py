@@ -11,22 +11,20 @@ install_depth_error_on_rays() puts it under the reference's name, once per head 
 trainer's make_result_dict runs them, with idx_img_rendered a device arange.
 Rows, for B in {3, 6, 9} maps of 300 x 400 with 2048 rays as ray_idx [B, 2048 // B]: `alone_B<B>`: on fixed render outputs;
 `render_B<B>`: behind a real render step of those rays at 64 + 128 samples in bf16x3 with a backward to both networks.  The legs of
-a row run in ONE process in alternating, non-overlapping blocks of `--iters` iterations (ten times as many in an `alone` row) after a
-warm-up of each; per leg ms per iteration (device events around a block; a readback stalls the host inside the block, so the figure
-is wall time as the device saw it) as median and min ... max over the blocks, each leg over `series`, and whether their blocks overlap.
+a row run in the alternating blocks of tools/paired_bench.py, of `--iters` iterations (ten times as many in an `alone` row); per leg
+ms per iteration as median and min ... max over the blocks, each leg over `series`, and whether their blocks overlap.
 `--trace-only` (a run of its own: tracing slows the host) times nothing: it traces ONE iteration of the depth errors of each leg of
-every `alone` row after the warm-up with the profiler and reports the kernels, the copies under the profiler's labels, the readbacks
--- counted where they are asked for: an `aten::nonzero` (the boolean selection reads its count) or an `.item()` -- and the runtime's
-blocking calls (a blocking copy is a readback or the upload of a host index), under `traced_iteration`.  One JSON document on stdout and, with --out, in that file
+every `alone` row after the warm-up (paired_bench's profiler pass) and reports the kernels, the copies under the profiler's labels,
+the readbacks where they are asked for and the host waits (a blocking copy is a readback or the upload of a host index), without any
+device synchronise, under `traced_iteration`.  One JSON document on stdout and, with --out, in that file
 (a --trace-only run adds its key to the document already there)."""
-import argparse
 import contextlib
-import json
 import os
-import statistics
 import sys
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -107,82 +105,44 @@ class Work:
         return [float(v) for v in self.values]
 
 
-def block(work, iters):
-    """-> ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def traced(work):
-    """-> the device activities of the depth errors of ONE iteration, from the profiler's trace: kernels, copies and memsets, the
-    readbacks and the runtime calls that make the host wait (synchronisations and blocking copies)"""
-    from torch.profiler import ProfilerActivity, profile
+    """-> the device activities of the depth errors of ONE iteration (paired_bench.traced): kernels, copies and memsets, the readbacks
+    where they are asked for and the runtime calls that make the host wait, without every device synchronise (the profiler's own too)"""
     out = work.step()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        depth_errors(work.leg, work.data, out)
-        torch.cuda.synchronize()
-    events = list(prof.events())
-    names = [e.name for e in events if str(e.device_type).endswith("CUDA")]
-    copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-    host = [e.name for e in events if not str(e.device_type).endswith("CUDA")]
-    # a readback, counted where it is asked for: the nonzero behind a boolean selection reads its count, .item() its value
-    readbacks = sum(1 for x in host if x in ("aten::nonzero", "aten::_local_scalar_dense"))
-    # the runtime calls that make the host wait, without the synchronise that ends the traced window (and the profiler's own)
-    waits = [x for x in host if x.startswith(("hip", "cuda")) and "DeviceSynchronize" not in x and
-             ("Synchronize" in x or ("Memcpy" in x and "Async" not in x))]
-    return dict(kernels=len(names) - len(copies), copies_and_memsets=len(copies), copies_by_label={x: copies.count(x) for x in sorted(set(copies))},
-                readbacks=readbacks, host_waits=len(waits), host_waits_by_name={x: waits.count(x) for x in sorted(set(waits))})
+    t = pb.traced(lambda: depth_errors(work.leg, work.data, out), host=True, every_device_sync=True)
+    return dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies), copies_by_label=t.copies_by_label, readbacks=t.readbacks_asked,
+                host_waits=len(t.host_waits), host_waits_by_name={x: t.host_waits.count(x) for x in sorted(set(t.host_waits))})
 
 
 def measure(works, blocks, iters, warmup):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    ms = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            ms[k].append(block(w, iters))
-    out = {k: dict(ms_per_iter_median=statistics.median(t), ms_per_iter_min=min(t), ms_per_iter_max=max(t), ms_per_iter_blocks=t) for k, t in ms.items()}
+    ms = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: pb.flat(t) for k, t in ms.items()}
     out["result"] = {k: w.result() for k, w in works.items()}
     for k in LEGS[1:]:
-        out[f"{k}_over_series"] = out[k]["ms_per_iter_median"] / out["series"]["ms_per_iter_median"]
-        out[f"{k}_and_series_blocks_overlap"] = out[k]["ms_per_iter_max"] >= out["series"]["ms_per_iter_min"]
-        out[f"series_minus_{k}_ms"] = out["series"]["ms_per_iter_median"] - out[k]["ms_per_iter_median"]
+        ratio, less, overlap = pb.versus(ms["series"], ms[k])
+        out.update({f"{k}_over_series": ratio, f"{k}_and_series_blocks_overlap": overlap, f"series_minus_{k}_ms": less})
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--rows", nargs="+", default=["alone", "render"], choices=["alone", "render"])
     ap.add_argument("--batches", nargs="+", type=int, default=[3, 6, 9])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--trace-only", action="store_true", help="trace one iteration of each leg with the profiler; time nothing")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/depth_err_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/depth_err_bench.py")
     rows = {}
     for B in a.batches:
         for kind in (["alone"] if a.trace_only else a.rows):
             works = {leg: Work(leg, B, device, kind == "render") for leg in LEGS}
             if a.trace_only:
                 for w in works.values():
-                    block(w, a.warmup)
+                    pb.device_block(w, a.warmup)
                 rows[f"{kind}_B{B}"] = {leg: traced(w) for leg, w in works.items()}
             else:
                 rows[f"{kind}_B{B}"] = measure(works, a.blocks, a.iters * (ALONE_ITERS if kind == "alone" else 1), a.warmup)
     if a.trace_only:
-        doc = json.load(open(a.out)) if a.out and os.path.exists(a.out) else dict(tool="tools/depth_err_bench.py --trace-only")
+        doc = pb.existing(a.out, dict(tool="tools/depth_err_bench.py --trace-only"))
         doc["traced_iteration"] = rows
     else:
         doc = dict(tool="tools/depth_err_bench.py", label=a.label, device=torch.cuda.get_device_name(0),
@@ -190,12 +150,7 @@ def main():
                             "idx_img_rendered a device arange; alone_B<B>: on fixed render outputs; render_B<B>: behind a real render step (bf16x3, "
                             "64 + 128 samples) with its backward",
                    blocks=a.blocks, iters_per_block=a.iters, alone_iters_per_block=ALONE_ITERS * a.iters, warmup_iters=a.warmup, legs=list(LEGS), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

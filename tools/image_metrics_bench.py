@@ -10,17 +10,15 @@ reference's own functions read back 5 to 14 times per head.  `fused`: one two-he
 vector.
 Rows: one view (B = 1) of 300 x 400 and of 378 x 504; `plain` (PSNR and SSIM only) and `all` (foreground mask and depth errors at a scale
 of 1.37 as well); `alone` on fixed render outputs and `render` behind a full-image render at 64 + 128 samples in bf16x3 under no_grad.
-The legs of a row run in ONE process in alternating, non-overlapping blocks after a warm-up of each.  Per leg: device ms per iteration
-(device events around a block, which ends in a synchronise) as median and min ... max over the blocks, and whether the legs' ranges
-overlap.  --trace-only, in a run of its own: the kernels, copies and readbacks (device-to-host copies) of ONE iteration of each `alone`
-row from the profiler's trace, merged into the document of --out.  One JSON document on stdout and, with --out, in that file."""
-import argparse
-import json
+The legs of a row run in the alternating blocks of tools/paired_bench.py.  Per leg: device ms per iteration as median and min ... max
+over the blocks, and whether the legs' ranges overlap.  --trace-only, in a run of its own: the kernels, copies and readbacks
+(device-to-host copies, by label) of ONE iteration of each `alone` row (paired_bench's profiler pass), merged into the document of --out.  One JSON document on stdout and, with --out, in that file."""
 import os
-import statistics
 import sys
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "compat")]
@@ -103,47 +101,17 @@ class BehindRender:
         return evaluate(self.leg, self.data, out, self.H, self.W, self.all_terms)
 
 
-def block(work, iters):
-    """-> device ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def launches(work):
-    """the device activities of ONE iteration from the profiler's trace -> dict(kernels, copies_and_memsets, readbacks)"""
-    from torch.profiler import ProfilerActivity, profile
+    """the device activities of ONE iteration (paired_bench.traced) -> dict(kernels, copies_and_memsets, readbacks by label)"""
     work.iteration()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        work.iteration()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
-    copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-    return dict(kernels=len(names) - len(copies), copies_and_memsets=len(copies), readbacks=sum("dtoh" in x.lower() for x in copies))
-
-
-def summary(values):
-    return dict(median=statistics.median(values), min=min(values), max=max(values), blocks=values)
+    t = pb.traced(work.iteration)
+    return dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies), readbacks=t.readbacks_by_label)
 
 
 def measure(works, blocks, iters, warmup):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    dev = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            dev[k].append(block(w, iters))
-    out = {k: dict(device_ms_per_iter=summary(dev[k])) for k in works}
-    s, f = out["series"]["device_ms_per_iter"], out["fused"]["device_ms_per_iter"]
-    out["fused_over_series_device"] = f["median"] / s["median"]
-    out["series_minus_fused_device_ms"] = s["median"] - f["median"]
-    out["blocks_overlap"] = f["max"] >= s["min"]
+    dev = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: dict(device_ms_per_iter=pb.summary(dev[k])) for k in works}
+    out["fused_over_series_device"], out["series_minus_fused_device_ms"], out["blocks_overlap"] = pb.versus(dev["series"], dev["fused"])
     return out
 
 
@@ -154,21 +122,14 @@ def agreement(works):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__, warmup=3)
     ap.add_argument("--rows", nargs="+", default=["alone", "render"], choices=["alone", "render"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--render-iters", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trace-only", action="store_true", help="only the launch counts of the `alone` rows, merged into the document of --out")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/image_metrics_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/image_metrics_bench.py")
     if a.trace_only:
-        doc = json.load(open(a.out)) if a.out and os.path.exists(a.out) else dict(tool="tools/image_metrics_bench.py", rows={})
+        doc = pb.existing(a.out, dict(tool="tools/image_metrics_bench.py", rows={}))
         for H, W in SIZES:
             for terms, all_terms in (("plain", False), ("all", True)):
                 row = doc["rows"].setdefault(f"alone_{H}x{W}_{terms}", {})
@@ -190,12 +151,7 @@ def main():
                    blocks=a.blocks, iters_per_block=a.iters, render_iters_per_block=a.render_iters, warmup_iters=a.warmup,
                    legs=dict(series="metrics.compute_metrics under metrics.unfused(), coarse head then fine head, trivial lpips_loss",
                              fused="one two-head metrics.image_metrics call + the readback of its vector"), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -13,22 +13,20 @@ Rows, at 300 x 400 with max_matches = 512 and at 378 x 504 with max_matches = 10
 configurations for 360-degree and forward-facing data), in the pre-crop phase (window of precrop_frac 0.5) on a mask that keeps about
 40 % of the pixels: `sampler_<H>x<W>`: select_matches alone; `whole_<H>x<W>`: losses.compute_loss_on_image_pair on a stand-in around a
 real Graph -- the sampler, two renders of max_matches pixels at 64 + 128 samples in bf16x3, the loss, backward to poses and networks.
-Both legs of a row run in ONE process in alternating blocks of `--iters` iterations (ten times as many in a sampler row) after a warm-up of each; per leg ms per iteration
-(device events around a block; the sampler's readback stalls the host inside the block, so the figure is wall time as the device saw it)
-as median and min ... max over the blocks, `fused` over `series`, and whether their blocks overlap.  After the timed blocks each leg
+The legs of a row run in the alternating blocks of tools/paired_bench.py, of `--iters` iterations (ten times as many in a sampler row);
+per leg ms per iteration as median and min ... max over the blocks, `fused` over `series`, and whether their blocks overlap.  After the timed blocks each leg
 runs one more iteration from the same seed; the count, the selected ray indices' checksum and, in a whole row, the loss are reported.
-`--count-launches` (a run of its own) traces ONE sampler-alone iteration of each leg after the warm-up with the profiler and reports the
-kernels, copies and memsets it launched and the runtime's synchronising calls; it times nothing.
+`--count-launches` (a run of its own) traces ONE sampler-alone iteration of each leg after the warm-up (paired_bench's profiler pass) and
+reports the kernels, copies and memsets it launched and the host waits; it times nothing.
 One JSON document on stdout and, with --out, in that file."""
-import argparse
 import contextlib
-import json
 import os
-import statistics
 import sys
 import types
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -130,84 +128,42 @@ class Whole:
         return {k: float(v) for k, v in self.report.items()}
 
 
-def block(work, iters):
-    """-> ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def measure(works, blocks, iters, warmup):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    ms = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            ms[k].append(block(w, iters))
-    out = {k: dict(ms_per_iter_median=statistics.median(t), ms_per_iter_min=min(t), ms_per_iter_max=max(t), ms_per_iter_blocks=t) for k, t in ms.items()}
+    ms = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: pb.flat(t) for k, t in ms.items()}
     out["result"] = {}
     for k, w in works.items():                                 # the reported iteration: every leg from the same generator state
         torch.manual_seed(0)
         w.iteration()
         out["result"][k] = w.result()
-    out["fused_over_series"] = out["fused"]["ms_per_iter_median"] / out["series"]["ms_per_iter_median"]
-    out["fused_and_series_blocks_overlap"] = out["fused"]["ms_per_iter_max"] >= out["series"]["ms_per_iter_min"]
-    out["series_minus_fused_ms"] = out["series"]["ms_per_iter_median"] - out["fused"]["ms_per_iter_median"]
-    if "body" in out:
-        out["body_minus_fused_ms"] = out["body"]["ms_per_iter_median"] - out["fused"]["ms_per_iter_median"]
-        out["fused_and_body_blocks_overlap"] = out["fused"]["ms_per_iter_max"] >= out["body"]["ms_per_iter_min"]
+    ratio, less, overlap = pb.versus(ms["series"], ms["fused"])
+    out.update(fused_over_series=ratio, fused_and_series_blocks_overlap=overlap, series_minus_fused_ms=less)
+    if "body" in ms:
+        _, less, overlap = pb.versus(ms["body"], ms["fused"])
+        out.update(body_minus_fused_ms=less, fused_and_body_blocks_overlap=overlap)
     return out
 
 
 def count_launches(device, H, W, warmup):
-    """-> per leg the device activities of ONE sampler-alone iteration after the warm-up, from the profiler's trace: kernels, memory
-    copies and memsets with the kernels' names, and the runtime calls that make the host wait (synchronisations and blocking copies)"""
-    from torch.profiler import ProfilerActivity, profile
+    """-> per leg the device activities of ONE sampler-alone iteration after the warm-up (paired_bench.traced): kernels, memory copies
+    and memsets with the kernels' names, and the host waits"""
     works = {leg: Sampler(leg, H, W, device) for leg in LEGS}
     for w in works.values():
-        block(w, warmup)
+        pb.device_block(w, warmup)
     out = {}
     for leg, w in works.items():
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            w.iteration()
-            torch.cuda.synchronize()
-        events = list(prof.events())
-        names = [e.name for e in events if str(e.device_type).endswith("CUDA")]
-        copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-        kernels = [x for x in names if x not in copies]
-        waits = [e.name for e in events if not str(e.device_type).endswith("CUDA") and e.name.startswith(("hip", "cuda")) and
-                 ("Synchronize" in e.name or ("Memcpy" in e.name and "Async" not in e.name))]
-        for own in ("hipDeviceSynchronize", "cudaDeviceSynchronize"):           # the one that ends the traced window
-            if own in waits:
-                waits.remove(own)
-                break
-        hist = {}
-        for x in kernels:
-            hist[x[:80]] = hist.get(x[:80], 0) + 1
-        out[leg] = dict(kernels=len(kernels), copies_and_memsets=len(copies), copies_by_name=sorted(copies), host_waits=len(waits),
-                        host_waits_by_name=sorted(waits), by_name=hist)
+        t = pb.traced(w.iteration, host=True)
+        out[leg] = dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies), copies_by_name=sorted(t.copies), host_waits=len(t.host_waits),
+                        host_waits_by_name=t.host_waits, by_name=t.by_name)
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--rows", nargs="+", default=["sampler", "whole"], choices=["sampler", "whole"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--count-launches", action="store_true")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/match_select_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/match_select_bench.py")
     if a.count_launches:
         doc = dict(tool="tools/match_select_bench.py --count-launches", device=torch.cuda.get_device_name(0),
                    launches_per_iteration={f"{H}x{W}": count_launches(device, H, W, a.warmup) for H, W in SIZES})
@@ -224,12 +180,7 @@ def main():
                             "loss with the fine term) and its backward",
                    max_matches={f"{H}x{W}": m for (H, W), (m, _) in SIZES.items()},
                    blocks=a.blocks, iters_per_block=a.iters, sampler_iters_per_block=SAMPLER_ITERS * a.iters, warmup_iters=a.warmup, legs=list(LEGS), whole_legs=list(WHOLE_LEGS), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

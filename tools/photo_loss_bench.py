@@ -10,19 +10,16 @@ also leaves the two MSEs.
 Rows, all at 4 x 1024 rays (B = 4 images of 300 x 400, one shared list of 1024 ray indices), Huber: `alone_all` / `alone_colour`: the
 module and its backward on fixed render outputs, with every term on (mask and P = 2) or the colour term only; `render_all` /
 `render_colour`: the same behind a 4096-ray render at 64 + 128 samples in bf16x3, backward to both networks.
-The legs of a row run in ONE process in alternating, non-overlapping blocks of `--iters` iterations after a warm-up of each.  Per leg:
-device ms per iteration (device events around a block, which ends in a synchronise) and host ms per iteration (the host clock around the
-enqueue of the same block, before the synchronise), each as median and min ... max over the blocks; after the timed blocks, the kernels
-and copies of ONE iteration of the module alone from the profiler's kernel trace.  The comparison is `fused` against `trainer` of the
+The legs of a row run in the alternating blocks of tools/paired_bench.py, of `--iters` iterations.  Per leg: device ms per iteration
+and host ms per iteration (the host clock around the enqueue of the same block), each as median and min ... max over the blocks; after
+the timed blocks, the kernels and copies of ONE iteration of the module alone (paired_bench's profiler pass).  The comparison is `fused` against `trainer` of the
 same row.  One JSON document on stdout and, with --out, in that file."""
-import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -117,72 +114,28 @@ class BehindRender:
         return loss
 
 
-def block(work, iters):
-    """-> (device ms, host ms) per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    host = (time.perf_counter() - t0) * 1e3
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters, host / iters
-
-
-def launches(work):
-    """the device activities of ONE iteration from the profiler's kernel trace -> dict(kernels, copies_and_memsets)"""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        work.iteration()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
-    copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-    return dict(kernels=len(names) - len(copies), copies_and_memsets=len(copies))
-
-
-def summary(values):
-    return dict(median=statistics.median(values), min=min(values), max=max(values), blocks=values)
-
-
 def measure(works, blocks, iters, warmup, count):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    dev, host = {k: [] for k in works}, {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            d, h = block(w, iters)
-            dev[k].append(d)
-            host[k].append(h)
-    out = {k: dict(device_ms_per_iter=summary(dev[k]), host_ms_per_iter=summary(host[k])) for k in works}
+    timed = pb.alternate(works, blocks, iters, warmup)
+    dev, host = ({k: [v[i] for v in t] for k, t in timed.items()} for i in (0, 1))
+    out = {k: dict(device_ms_per_iter=pb.summary(dev[k]), host_ms_per_iter=pb.summary(host[k])) for k in works}
     for k, w in works.items():
         torch.manual_seed(0)
         out[k]["loss"] = float(w.iteration().detach())
         out[k]["mse"] = [float(m) for m in w.mse]
-        if count:
-            out[k]["launches_per_iteration"] = launches(w)
-    a, c = out["trainer"]["device_ms_per_iter"], out["fused"]["device_ms_per_iter"]
-    out["fused_over_trainer_device"] = c["median"] / a["median"]
-    out["fused_over_trainer_host"] = out["fused"]["host_ms_per_iter"]["median"] / out["trainer"]["host_ms_per_iter"]["median"]
-    out["trainer_minus_fused_device_ms"] = a["median"] - c["median"]
-    out["fused_and_trainer_blocks_overlap"] = c["max"] >= a["min"]
+        if count:                                              # the kernels and copies of ONE iteration (paired_bench.traced)
+            t = pb.traced(w.iteration)
+            out[k]["launches_per_iteration"] = dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies))
+    ratio, less, overlap = pb.versus(dev["trainer"], dev["fused"])
+    out.update(fused_over_trainer_device=ratio, fused_over_trainer_host=pb.versus(host["trainer"], host["fused"])[0],
+               trainer_minus_fused_device_ms=less, fused_and_trainer_blocks_overlap=overlap)
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--rows", nargs="+", default=["alone", "render"], choices=["alone", "render"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/photo_loss_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/photo_loss_bench.py")
     rows = {}
     for terms, all_terms in (("all", True), ("colour", False)):
         if "alone" in a.rows:
@@ -196,12 +149,7 @@ def main():
                blocks=a.blocks, iters_per_block=a.iters, warmup_iters=a.warmup, legs=dict(trainer="(a) torch restatement + compute_mse_on_rays",
                                                                                           today="(b) ops.photometric_loss on a torch-gathered target + torch mask / patch terms + compute_mse_on_rays",
                                                                                           fused="(c) losses.photo_and_regu_loss"), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -11,22 +11,20 @@ random similarity, and the readback of its four values as the logger makes it.  
 (:728-739) at one pose: backtrack_from_aligning_the_trajectory, then camera.pose.compose with the refinement, no readback.
 `chain_in_loop`: the same chain inside the test-time optimisation loop of tools/pose_optim_bench.py's view (4096 rays, 64 + 128
 samples, bf16x3, the full route), called twice per iteration as the trainer does (:394 and :397), se3_to_SE3 on its kernel in both legs.
-The legs of a row run in ONE process in alternating, non-overlapping blocks after a warm-up of each.  Per leg: device ms per call (device
-events around a block, which ends in a synchronise) as median and min ... max over the blocks, and whether the legs' ranges overlap.
---trace-only, in a run of its own: the kernels, copies and readbacks (device-to-host copies) of ONE call of each row but the loop from the
-profiler's trace, merged into the document of --out; `item_calls_in_code` adds the series' `.item()` synchronisations, which the trace does
+The legs of a row run in the alternating blocks of tools/paired_bench.py.  Per leg: device ms per call as median and min ... max over
+the blocks, and whether the legs' ranges overlap.
+--trace-only, in a run of its own: the kernels, copies and readbacks (device-to-host copies, by label) of ONE call of each row but the
+loop (paired_bench's profiler pass), merged into the document of --out; `item_calls_in_code` adds the series' `.item()` synchronisations, which the trace does
 not list as device copies, counted from its code.  One JSON line on stdout per run and, with --out, the document in that file."""
-import argparse
 import contextlib
-import json
 import os
-import statistics
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "compat"), os.path.join(ROOT, "tools")]
+import paired_bench as pb                                                      # noqa: E402
 from sparf_amd import camera, pose_eval                                        # noqa: E402
 from sparf_amd.edict import EasyDict as edict                                  # noqa: E402
 
@@ -118,70 +116,30 @@ def chain_in_loop(leg, device):
     return ChainView()
 
 
-def block(work, iters):
-    """-> device ms per iteration of `iters` iterations"""
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        work.iteration()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def launches(work):
-    """the device activities of ONE iteration from the profiler's trace -> dict(kernels, copies_and_memsets, readbacks)"""
-    from torch.profiler import ProfilerActivity, profile
+    """the device activities of ONE iteration (paired_bench.traced) -> dict(kernels, copies_and_memsets, readbacks by label, ...)"""
     work.iteration()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        work.iteration()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
-    copies = [x for x in names if x.lower().startswith(("memcpy", "memset"))]
-    kinds = {}
-    for x in copies:
-        kinds[x] = kinds.get(x, 0) + 1
-    return dict(kernels=len(names) - len(copies), copies_and_memsets=len(copies), readbacks=sum("dtoh" in x.lower() for x in copies), copy_kinds=kinds,
-                item_calls_in_code=getattr(work, "item_calls", 0))
-
-
-def summary(values):
-    return dict(median=statistics.median(values), min=min(values), max=max(values), blocks=values)
+    t = pb.traced(work.iteration)
+    return dict(kernels=len(t.kernels), copies_and_memsets=len(t.copies), readbacks=t.readbacks_by_label,
+                copy_kinds={x: t.copies.count(x) for x in dict.fromkeys(t.copies)}, item_calls_in_code=getattr(work, "item_calls", 0))
 
 
 def measure(works, blocks, iters, warmup):
-    for w in works.values():                                   # warm-up of every shape the timed window uses
-        block(w, warmup)
-    dev = {k: [] for k in works}
-    for _ in range(blocks):                                    # alternating blocks: every leg sees the same minutes of the machine
-        for k, w in works.items():
-            dev[k].append(block(w, iters))
-    out = {k: dict(device_ms_per_call=summary(dev[k])) for k in works}
-    s, f = out["series"]["device_ms_per_call"], out["fused"]["device_ms_per_call"]
-    out["fused_over_series_device"] = f["median"] / s["median"]
-    out["series_minus_fused_device_ms"] = s["median"] - f["median"]
-    out["blocks_overlap"] = f["max"] >= s["min"]
+    dev = pb.device_ms(works, blocks, iters, warmup)
+    out = {k: dict(device_ms_per_call=pb.summary(dev[k])) for k in works}
+    out["fused_over_series_device"], out["series_minus_fused_device_ms"], out["blocks_overlap"] = pb.versus(dev["series"], dev["fused"])
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__, warmup=3)
     ap.add_argument("--rows", nargs="+", default=["evaluate", "chain", "loop"], choices=["evaluate", "chain", "loop"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--loop-iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trace-only", action="store_true", help="only the launch counts of the evaluate and chain rows, merged into the document of --out")
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/pose_eval_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/pose_eval_bench.py")
     if a.trace_only:
-        doc = json.load(open(a.out)) if a.out and os.path.exists(a.out) else dict(tool="tools/pose_eval_bench.py", rows={})
+        doc = pb.existing(a.out, dict(tool="tools/pose_eval_bench.py", rows={}))
         for B in VIEWS:
             doc["rows"].setdefault(f"evaluate_B{B}", {})["launches_per_call"] = {leg: launches(Evaluate(leg, B, device)) for leg in LEGS}
         doc["rows"].setdefault("chain_alone", {})["launches_per_call"] = {leg: launches(ChainAlone(leg, device)) for leg in LEGS}
@@ -203,12 +161,7 @@ def main():
                    blocks=a.blocks, calls_per_block=a.iters, loop_iters_per_block=a.loop_iters, warmup_calls=a.warmup,
                    legs=dict(series="the torch restatement under pose_eval.unfused() and camera.unfused(): the reference's pair loop, backtrack and compose",
                              fused="sparf_pose_eval / sparf_pose_backtrack / the compose kernel"), rows=rows)
-    text = json.dumps(doc, indent=1)
-    print(json.dumps(doc))                                     # one line per run
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out, one_line=True)                         # one line per run
 
 
 if __name__ == "__main__":

@@ -7,20 +7,18 @@ The loop, the view and the two routes (`full`, `rays_only` = opt.hip.test_optim_
 `View` this tool subclasses; what changes is how the 6-vector becomes the pose.  `closed`: the closed-form twist exponential of
 bench_workloads.se3_exp, i.e. exactly what tools/test_optim_bench.py runs.  `series`: the reference's own chain, camera.lie.se3_to_SE3
 (truncated series) then camera.pose.compose, as the torch restatement of sparf_amd.camera -- what an unmodified trainer runs.  `fused`:
-sparf_amd.camera.refine_se3, one launch each way.  Every (route, pose) pair runs in ONE process in alternating blocks of `--iters`
-iterations after a warm-up of each, keyed "<route>" for closed and "<route>+<pose>" otherwise; per pair ms per iteration as median and
+sparf_amd.camera.refine_se3, one launch each way.  Every (route, pose) pair runs in the alternating blocks of tools/paired_bench.py, of
+`--iters` iterations, keyed "<route>" for closed and "<route>+<pose>" otherwise; per pair ms per iteration as median and
 min ... max over the blocks, and per route `fused` over `series` with whether their blocks overlap.
 One JSON document on stdout and, with --out, in that file."""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import paired_bench as pb                                     # noqa: E402
 from bench_workloads import compose, se3_exp                  # noqa: E402
 from sparf_amd import camera                                  # noqa: E402
 from test_optim_bench import HAS_ROUTE, View                  # noqa: E402
@@ -58,43 +56,24 @@ def measure(precision, device, blocks, iters, warmup, poses):
     for route, rays_only in (("full", False),) + ((("rays_only", True),) if HAS_ROUTE else ()):
         for pm in poses:
             views[route if pm == "closed" else route + "+" + pm] = PoseView(precision, rays_only, device, pm)
-    for v in views.values():                                   # warm-up of every shape the timed window uses
-        v.block(warmup)
-    ms = {k: [] for k in views}
-    for _ in range(blocks):                                    # alternating blocks: every pair sees the same minutes of the machine
-        for k, v in views.items():
-            ms[k].append(v.block(iters)[0])
-    out = {k: dict(ms_per_iter_median=statistics.median(t), ms_per_iter_min=min(t), ms_per_iter_max=max(t), ms_per_iter_blocks=t) for k, t in ms.items()}
+    ms = pb.device_ms(views, blocks, iters, warmup)
+    out = {k: pb.flat(t) for k, t in ms.items()}
     for route in ("full", "rays_only"):
-        s, f = out.get(route + "+series"), out.get(route + "+fused")
-        if s and f:
-            out[route + "_fused_over_series"] = f["ms_per_iter_median"] / s["ms_per_iter_median"]
-            out[route + "_fused_and_series_blocks_overlap"] = f["ms_per_iter_max"] >= s["ms_per_iter_min"]
+        if route + "+series" in ms and route + "+fused" in ms:
+            out[route + "_fused_over_series"], _, out[route + "_fused_and_series_blocks_overlap"] = pb.versus(ms[route + "+series"], ms[route + "+fused"])
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--pose", nargs="+", default=list(POSES), choices=POSES)
     ap.add_argument("--precisions", nargs="+", default=["bf16x3", "fp32"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/pose_optim_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/pose_optim_bench.py")
     doc = dict(tool="tools/pose_optim_bench.py", label=a.label, device=torch.cuda.get_device_name(0), workload="one DTU-shaped test view, 4096 rays x (64 + 128), "
                "Adam on a 6-vector, mode test-optim", blocks=a.blocks, iters_per_block=a.iters, warmup_iters=a.warmup, pose=a.pose,
                precisions={p: measure(p, device, a.blocks, a.iters, a.warmup, tuple(a.pose)) for p in a.precisions})
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":

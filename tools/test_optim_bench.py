@@ -5,18 +5,17 @@
 The loop is the reference's (joint_pose_nerf_trainer.py:381-406): per test view, Adam on a zero-initialised 6-vector composed with the
 view's initial pose, 4096 random rays x (64 + 128) samples of a DTU-shaped 300 x 400 view per iteration, render in mode "test-optim",
 photometric loss on both networks' colours, backward, Adam step.  The networks stay trainable, as in the unmodified loop; the option
-alone selects the route, so BOTH routes run in ONE process, in alternating blocks of `--iters` iterations after a warm-up of each.
-Per route and precision: ms per iteration (render + backward + Adam step; device events around a block, so a block ends in a
-synchronise) as median and spread (min ... max) over the blocks, and the peak allocated bytes of the route's blocks.
+alone selects the route, so BOTH routes run in ONE process, in the alternating blocks of tools/paired_bench.py, of `--iters` iterations.
+Per route and precision: ms per iteration (render + backward + Adam step) as median and spread (min ... max) over the blocks, and the
+peak allocated bytes of the route's blocks.
 On a tree without the option (an older commit) only the full route runs: the same numbers, comparable between commits.
 One JSON document on stdout and, with --out, in that file."""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
+
+import paired_bench as pb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -62,62 +61,38 @@ class View:
         self.optim.step()
         return loss
 
-    def block(self, iters):
-        """-> (ms per iteration, peak allocated bytes) of `iters` iterations"""
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            self.iteration()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters, torch.cuda.max_memory_allocated()
+
+def block_with_peak(view, iters):
+    """paired_bench.device_block -> (ms per iteration, peak allocated bytes) of `iters` iterations"""
+    torch.cuda.reset_peak_memory_stats()
+    ms, _ = pb.device_block(view, iters)
+    return ms, torch.cuda.max_memory_allocated()
 
 
 def measure(precision, device, blocks, iters, warmup):
     routes = {"full": View(precision, False, device)}
     if HAS_ROUTE:
         routes["rays_only"] = View(precision, True, device)
-    for v in routes.values():                                          # warm-up of every shape the timed window uses
-        v.block(warmup)
-    ms = {k: [] for k in routes}
-    peak = {k: 0 for k in routes}
-    for _ in range(blocks):                                            # alternating blocks: both routes see the same minutes of the machine
-        for k, v in routes.items():
-            t, p = v.block(iters)
-            ms[k].append(t)
-            peak[k] = max(peak[k], p)
+    timed = pb.alternate(routes, blocks, iters, warmup, block=block_with_peak)
+    ms = {k: [t for t, _ in v] for k, v in timed.items()}
     out = {}
     for k in routes:
-        out[k] = dict(ms_per_iter_median=statistics.median(ms[k]), ms_per_iter_min=min(ms[k]), ms_per_iter_max=max(ms[k]), ms_per_iter_blocks=ms[k],
-                      peak_allocated_bytes=peak[k], network_grads_populated=all(p.grad is not None for p in routes[k].graph.nerf.hip_params()))
+        out[k] = dict(pb.flat(ms[k]), peak_allocated_bytes=max(p for _, p in timed[k]),
+                      network_grads_populated=all(p.grad is not None for p in routes[k].graph.nerf.hip_params()))
     if HAS_ROUTE:
-        out["rays_only_over_full"] = out["rays_only"]["ms_per_iter_median"] / out["full"]["ms_per_iter_median"]
+        out["rays_only_over_full"] = pb.versus(ms["full"], ms["rays_only"])[0]
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
+    ap = pb.parser(__doc__)
     ap.add_argument("--precisions", nargs="+", default=["bf16x3", "fp32"])
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--label", default=None, help="free text kept in the document (which commit this tree is)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/test_optim_bench.py measures on the GPU: no device found")
-    device = torch.device("cuda:0")
+    device = pb.gpu_or_exit("tools/test_optim_bench.py")
     doc = dict(tool="tools/test_optim_bench.py", label=a.label, device=torch.cuda.get_device_name(0), workload="one DTU-shaped test view, 4096 rays x (64 + 128), "
                "Adam on a 6-vector, mode test-optim", blocks=a.blocks, iters_per_block=a.iters, warmup_iters=a.warmup, has_rays_only_route=HAS_ROUTE,
                precisions={p: measure(p, device, a.blocks, a.iters, a.warmup) for p in a.precisions})
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    pb.emit(doc, a.out)
 
 
 if __name__ == "__main__":
